@@ -9,15 +9,22 @@ one-pass fp64 advantage moments and the advantage normalisation (the only cross-
 all-gather of N x 3 doubles when --gpus > 1).  Inputs are in HBM before the timed region starts.
 That is BASELINE config 2 ("random policy, step-kernel only") plus the collector: `value`.
 
-The same JSON line carries a second record, `closed_loop` = BASELINE config 3 (config 4 when
+A plain run does what that figure needs and nothing else: set-up, warm-up, the timed steps, the result line
+(and, with --dump-outputs DIR, what the last timed step left in the rollout buffers as DIR/<name>.npy).
+
+With --full the same JSON line carries everything else the benchmark measures or checks: a second record,
+`closed_loop` = BASELINE config 3 (config 4 when
 --gpus > 1): the MPNN actor-critic in the loop (fa_collect_act: the fused forward + sampling kernel; the
 PyTorch module is its definition and fallback) -- per env-step one two-team forward, sampling and one
-fa_collect_step, then V(obs[T]), GAE and the advantage statistics -- and the PPO update after it.
+fa_collect_step, then V(obs[T]), GAE and the advantage statistics -- and the PPO update after it; the 5v5
+records, the E-sweep, the steady-state region, the live stream bandwidth and PMC traffic, the checks of the
+exchange routes against each other, the CPU baseline (each with its own --no-... switch).
 
     python bench.py --gpus 1 --steps 20 --warmup 3
-    python bench.py --gpus 8                      # spawns 8 ranks itself (torch.distributed.run)
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
+    python bench.py --gpus 8 --full               # spawns 8 ranks itself (torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
-        --master-port 29500 bench.py --gpus 8 --steps 20 --warmup 3
+        --master-port 29500 bench.py --gpus 8 --steps 20 --warmup 3 --full
 
 Prints ONE JSON line on rank 0.
 """
@@ -353,6 +360,32 @@ def _ranges(ids):
     return ",".join(out)
 
 
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000   # --dump-outputs writes at most this much, all files together
+
+
+def dump_outputs(dirname, st, adv, rank):
+    """--dump-outputs: what the timed path left in the buffers its caller reads, after its last timed step -- the rollout's
+    obs / rewards / masks / done rows and, with the collector tail, the GAE returns and the normalised advantages -- as
+    DIR/<name>.npy in float32 (ranks above 0: <name>_rank<r>.npy).  The default shape holds ~128 MB of them: above the
+    budget a fixed, seeded sample of the envs is written (the same envs in every array and in every run; envs.npy lists
+    them), every time step and every agent of each."""
+    import numpy as np
+    import torch
+    fields = [("obs", st.obs), ("rewards", st.rewards), ("masks", st.masks), ("done", st.done)]
+    if adv is not None:
+        fields += [("returns", st.returns), ("advantages", adv)]
+    E = st.num_processes
+    total = 4 * sum(t.numel() for _, t in fields) + 8 * E
+    keep = E if total <= DUMP_BUDGET_BYTES else max(1, E * DUMP_BUDGET_BYTES // total)
+    envs = np.arange(E) if keep == E else np.sort(np.random.RandomState(0).choice(E, keep, replace=False))
+    sel = torch.from_numpy(envs).to(st.obs.device)
+    os.makedirs(dirname, exist_ok=True)
+    suffix = "" if rank == 0 else "_rank%d" % rank
+    for name, t in fields:
+        np.save(os.path.join(dirname, name + suffix + ".npy"), t.index_select(1, sel).to(torch.float32).cpu().numpy())
+    np.save(os.path.join(dirname, "envs" + suffix + ".npy"), envs.astype(np.float64))
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without a launcher: start N ranks under torch.distributed.run (one
     process per GPU, rendezvous on 127.0.0.1) with the same arguments and pass their output through."""
@@ -371,6 +404,16 @@ def main():
     ap.add_argument("--steps", type=int, default=None,
                     help="rollouts to time: EXACTLY this many when given (default: 20, raised by --min-seconds)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: the closed_loop record, the 5v5 records, "
+                         "the E-sweep, the steady-state region, the live stream bandwidth and PMC traffic, the exchange routes "
+                         "against each other, the CPU baseline (the --no-... switches below take single ones out again).  "
+                         "Without it: set-up, warm-up, the timed steps, the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them left in the rollout buffers (obs, rewards, masks, "
+                         "done, returns, advantages) as DIR/<name>.npy, float32; a fixed seeded sample of the envs when all of "
+                         "them would exceed 60 MB.  Same arguments, same inputs: two builds can be compared output for output "
+                         "(without --steps exactly 20 steps are timed then, unless --min-seconds is given)")
     ap.add_argument("--min-seconds", type=float, default=None,
                     help="keep timing whole rollouts until the timed region is at least this long (the 128-step "
                          "rollout takes ~0.2 ms: 20 of them are a 4 ms sample).  Default: 0.5 when --steps is not "
@@ -431,6 +474,9 @@ def main():
         args.steps, args.warmup, args.min_seconds = 2, 1, 0.0
         args.closed_loop_rollouts, args.closed_loop_updates = 1, 1
         args.no_cpu_baseline = args.no_esweep = args.no_5v5 = args.no_live_traffic = True
+        args.full = True                       # (the self-check is about the closed loop and the update as well)
+    if not args.full:                          # a plain run: the headline figure only
+        args.no_cpu_baseline = args.no_closed_loop = args.no_esweep = args.no_5v5 = args.no_live_traffic = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args))
@@ -639,7 +685,9 @@ def main():
         hot_path()
         torch.cuda.synchronize()
     steps_requested = 20 if args.steps is None else args.steps
-    min_seconds = (0.5 if args.steps is None else 0.0) if args.min_seconds is None else args.min_seconds
+    # (--dump-outputs: the number of timed steps must not depend on the clock, or the last step's outputs would)
+    min_seconds = ((0.5 if args.steps is None and args.dump_outputs is None else 0.0) if args.min_seconds is None
+                   else args.min_seconds)
     steps = steps_requested
     if min_seconds > 0:
         t0 = time.perf_counter()
@@ -682,6 +730,8 @@ def main():
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:                         # behind the clock, ahead of everything else that runs the path again
+        dump_outputs(args.dump_outputs, st, None if args.no_collector else adv, rank)
     if hot_graph is not None:                     # the dominant kernel's launch time: eager launches right behind the timed region
         for k in range(steps):
             ev[k][0].record()
@@ -699,7 +749,7 @@ def main():
 
     # steady state: the driver's --steps 20 is a ~4 ms region; the same loop kept up for >= 0.5 s rides in the same line
     steady = None
-    if elapsed < 0.5 and not args.smoke:
+    if args.full and elapsed < 0.5 and not args.smoke:
         n2 = max(steps, int(0.55 / max(elapsed / steps, 1e-6)) + 1)
         if world > 1:
             ts = torch.tensor([n2], device=dev, dtype=torch.int64)
@@ -723,12 +773,12 @@ def main():
 
     # the second-stream exchange must leave what the one-stream form leaves (same launches, same order per buffer)
     pipelined_ok = None
-    if tail_stream is not None and not args.no_collector:
+    if args.full and tail_stream is not None and not args.no_collector:
         mean, std = gae_adv_mean_std(eng, 0.99, 0.95)
         pipelined_ok = bool(torch.equal(eng.adv_normalize(mean, std), adv))
     # ... and the library's one-call tail what the torch route leaves
     lib_route_ok = None
-    if lib_exchange is not None and not args.no_collector and tail_stream is None:
+    if args.full and lib_exchange is not None and not args.no_collector and tail_stream is None:
         mom, _, _ = eng.gae_moments(0.99, 0.95)
         dist.all_gather_into_tensor(gather_buf.view(-1), mom.view(-1))
         lib_route_ok = bool(torch.equal(eng.adv_merge_normalize(gather_buf)[0], adv))
@@ -765,7 +815,7 @@ def main():
         traffic, traffic_src = live_traffic(kernel_name.split("/")[0], args, device=local_rank)
         live_note = traffic_src
     else:
-        live_note = "not attempted (several ranks, per-step launches, or --no-live-traffic)"
+        live_note = "not attempted (a run without --full, several ranks, per-step launches, or --no-live-traffic)"
     if traffic is None and (E, G, A, T) == (4096, 3, 3, 128):
         for rnd in ("r05", "r04", "r03", "r02", "r01"):
             prof = os.path.join(ROOT, "profiles", "%s_%s_summary.json" % (rnd, "fused" if graph is None else "perstep"))
@@ -787,7 +837,7 @@ def main():
         res = {
             "metric": "env-steps/sec FortAttack %dv%d, %d parallel envs per GPU" % (G, A, E),
             "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": steps, "steps_requested": steps_requested,
-            "warmup": args.warmup, "ms_per_step": elapsed * 1e3 / steps, "timed_seconds": elapsed,
+            "warmup": args.warmup, "full": bool(args.full), "ms_per_step": elapsed * 1e3 / steps, "timed_seconds": elapsed,
             "host_enqueue_ms_per_step": host_enqueue * 1e3 / host_steps,   # < ms_per_step: the GPU, not the Python loop, sets the pace
             "host_enqueue_window_steps": host_steps,
             "higher_is_better": True,
@@ -818,7 +868,7 @@ def main():
                 "traffic_frac": (traffic / launch_s / 1e9 / HBM_PEAK_GBPS) if traffic else None,
                 "limiter": "instruction issue of the state's wave + two barrier round trips per step, not bandwidth, at this batch size: "
                            "see `secondary` and DESIGN.md 3.1 / 7",
-                "measured_stream_GBps": measured_stream(dev),
+                "measured_stream_GBps": measured_stream(dev) if args.full else None,
                 "algorithmic_bytes_per_launch": bytes_per_launch,
                 "algorithmic_bytes_per_env_step": algorithmic_bytes_per_env_step(N),
                 "env_steps_per_launch": E * (T // launches_per_rollout),

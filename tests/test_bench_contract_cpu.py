@@ -1,5 +1,5 @@
-"""CPU: the committed record of the driver's bench command (profiles/r06_bench_final.json, written on the GPU box by
-`python bench.py --gpus 1 --steps 20 --warmup 5`) carries every field the bench contract names, with consistent arithmetic --
+"""CPU: the committed record of the complete bench command (profiles/r06_bench_final.json, written on the GPU box by what is
+now `python bench.py --gpus 1 --steps 20 --warmup 5 --full`) carries every field the bench contract names, with consistent arithmetic --
 so that an edit of bench.py that drops or renames one shows up here, not at the end of a round."""
 import json
 import os

@@ -230,6 +230,44 @@ def test_update_forward_on_gpu_matches_reference_shaped_forward(fa, G, A):
         assert (ga - res[1][3][k]).abs().max() <= 2e-4 * max(1e-3, float(ga.abs().max())), k
 
 
+KINK_MARGIN = 2e-6
+
+
+def _smallest_relu_input(P, obs, own_sl, opp_sl):
+    """The smallest |relu input| of the trunk and the heads (mpnn_pack.folded_ppo_reference's forward) in float64."""
+    P = {k: v.detach().double() for k, v in P.items()}
+    own, opp = obs[:, own_sl].double(), obs[:, opp_sl].double()
+    n = own.shape[1]
+    z = [own @ P["WE"] + P["BE"], opp @ P["WOE"] + P["BOE"]]
+    h1, ho = torch.relu(z[0]), torch.relu(z[1])
+    att = torch.softmax((h1 @ P["AO"]) @ ho.transpose(1, 2), dim=-1)
+    h = torch.cat((h1, (att @ ho) @ P["BO"]), dim=2)
+    diag = torch.zeros(n, n, device=obs.device, dtype=torch.float64).fill_diagonal_(-float("inf"))
+    for _ in range(3):
+        mix = torch.softmax((h @ P["AM"]) @ h.transpose(1, 2) + diag, dim=-1) @ h if n > 1 else torch.zeros_like(h)
+        z.append(torch.cat((h, mix), dim=2) @ P["W7"] + P["BU"])
+        h = torch.relu(z[-1])
+    z.append(h @ P["W8"] + P["B8"])
+    return min(float(t.abs().min()) for t in z)
+
+
+def _obs_off_the_relu_kinks(P, B, N, seed, own_sl, opp_sl):
+    """_obs(B, N, seed), or the first of _obs(B, N, seed + 1000 k) whose float64 forward keeps every relu input at least
+    KINK_MARGIN from zero.  A relu input within float32 rounding of zero (sums of up to 256 products of O(1) terms: a few
+    1e-7) is positive in one float32 evaluation order and negative in another, and that unit's gradient passes or is blocked
+    accordingly -- both are float32 gradients of the same function, 1e-3 .. 1e-2 of a small tensor's largest entry apart
+    (a fixture for float32 gradients must not sit on a relu kink).  The batch (5, 5, 1, 200) at its
+    first seed has such an input, -8.5e-8 at (env 40, agent 4, unit 63) of the first update round, and the kernel and
+    torch's float32 autograd take different sides of it: the two differ in column 63 of dW7 / entry 63 of dBU and in
+    what flows back from there, nowhere else (float32 autograd == float64 autograd to 1.5e-6 there).  With B n rows x
+    770 relu units the search takes 1 .. 8 seeds for the small batches and ~250 (0.2 s) for B n = 1500."""
+    for k in range(2000):
+        obs = _obs(B, N, seed + 1000 * k)
+        if _smallest_relu_input(P, obs, own_sl, opp_sl) >= KINK_MARGIN:
+            return obs
+    raise AssertionError("no batch off the relu kinks in 2000 seeds")
+
+
 @pytest.mark.parametrize("G,A,team,B,clipped", [(3, 3, 0, 500, True), (3, 3, 1, 21, True), (3, 3, 0, 43, False),
                                                 (5, 5, 1, 200, True), (2, 4, 0, 100, True), (4, 2, 1, 77, True),
                                                 (8, 8, 0, 37, True), (7, 8, 1, 26, True), (1, 3, 0, 50, True)])
@@ -244,13 +282,13 @@ def test_fused_ppo_grad_matches_torch_autograd(fa, G, A, team, B, clipped):
     own_sl, opp_sl = (slice(0, G), slice(G, N)) if team == 0 else (slice(G, N), slice(0, G))
     n = G if team == 0 else A
     g = torch.Generator(device="cuda").manual_seed(B)
-    obs = _obs(B, N, B + 1)
     rnd = lambda *s: torch.randn(*s, device="cuda", generator=g)
     action = torch.randint(0, 8, (B, N, 1), device="cuda", generator=g)
     value_pred, ret, adv = rnd(B, N, 1), rnd(B, N, 1), rnd(B, N, 1)
     old_logp = -torch.rand((B, N, 1), device="cuda", generator=g) * 2.5
     clip, c_v, c_e = 0.2, 0.5, 0.01
     P = {k: v.detach().clone().requires_grad_(True) for k, v in mp_.kernel_params(pol).items()}
+    obs = _obs_off_the_relu_kinks(P, B, N, B + 1, own_sl, opp_sl)
     loss, vl, al, en, mm = mp_.folded_ppo_reference(P, obs, own_sl, opp_sl, action[:, own_sl], value_pred[:, own_sl], ret[:, own_sl],
                                                     old_logp[:, own_sl], adv[:, own_sl], clip, c_v, c_e, clipped)
     loss.backward()

@@ -209,8 +209,8 @@ def test_bench_exchange_on_rccl_with_one_rank():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-collective", "--two-stream-tail", "--backend", "nccl",
-                          "--envs", "1024", "--rollout", "32", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-5v5",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--full", "--force-collective", "--two-stream-tail", "--backend", "nccl",
+                          "--envs","1024", "--rollout", "32", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-5v5",
                           "--no-esweep", "--closed-loop-rollouts", "2", "--closed-loop-updates", "1"],
                          cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -232,8 +232,8 @@ def test_bench_library_exchange_one_call_per_rollout(graph):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-collective", "--backend", "nccl",
-                          "--envs", "1024", "--rollout", "32", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-5v5",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--full", "--force-collective", "--backend", "nccl",
+                          "--envs","1024", "--rollout", "32", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-5v5",
                           "--no-esweep", "--no-closed-loop", "--no-live-traffic"] + (["--graph-hot-path"] if graph else []),
                          cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]

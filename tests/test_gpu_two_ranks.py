@@ -297,7 +297,7 @@ def test_bench_self_launches_two_ranks():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-devices", "--backend",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--share-devices", "--backend",
                           "gloo", "--envs", "512", "--rollout", "32", "--steps", "3", "--warmup", "1",
                           "--no-cpu-baseline", "--closed-loop-rollouts", "1"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
@@ -319,7 +319,7 @@ def test_bench_eight_rank_rehearsal_on_one_gpu(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--share-devices", "--backend",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--full", "--share-devices", "--backend",
                           "gloo", "--envs", "512", "--rollout", "32", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
                           "--closed-loop-rollouts", "2", "--closed-loop-updates", "1"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
