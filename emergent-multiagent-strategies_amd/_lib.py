@@ -44,7 +44,8 @@ class Storage(C.Structure):
 class PolicyIO(C.Structure):
     _fields_ = [("obs", c_p), ("weights", c_p * 2), ("value", c_p), ("action", c_p), ("log_prob", c_p),
                 ("counter", c_p), ("seed", C.c_uint64), ("step", C.c_int32), ("deterministic", C.c_int32),
-                ("value_only", C.c_int32), ("attacker_pool", c_p), ("pool_size", C.c_int32), ("env_strategy", c_p)]
+                ("value_only", C.c_int32), ("attacker_pool", c_p), ("pool_size", C.c_int32), ("env_strategy", c_p),
+                ("team_attn", c_p * 2), ("opp_attn", c_p * 2)]   # attention export: NULL (the zero default) = not wanted
 
 
 class PPOGradIO(C.Structure):

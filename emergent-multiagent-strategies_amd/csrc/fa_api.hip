@@ -624,7 +624,8 @@ int fa_after_update(fa_env *env, void *stream) {
 
 static int policy_launch(fa_env *env, const float *obs, const float *wg, const float *wa, float *value, int64_t *action,
                          float *logp, const int64_t *counter, uint64_t seed, int step, int deterministic, int value_only,
-                         const float *pool, int pool_size, const int32_t *env_strategy, void *stream, const char *who) {
+                         const float *pool, int pool_size, const int32_t *env_strategy, float *const *team_attn,
+                         float *const *opp_attn, void *stream, const char *who) {
     if (!obs || !wg || (!wa && pool_size <= 0))
         return fail(FA_ERR_INVALID, std::string(who) + ": obs and both teams' weight buffers are required");
     if (!value_only && (!action || !logp)) return fail(FA_ERR_INVALID, std::string(who) + ": action and log_prob are required");
@@ -652,6 +653,10 @@ static int policy_launch(fa_env *env, const float *obs, const float *wg, const f
     a.step = step;
     a.deterministic = deterministic;
     a.value_only = value_only;
+    for (int t = 0; t < 2; ++t) { // attention export: any non-null pointer selects the exporting kernel
+        a.team_attn[t] = team_attn[t];
+        a.opp_attn[t] = opp_attn[t];
+    }
     if (pool_size > 0) { // group the envs into tiles of equal strategy, then one launch over the grouped tiles
         FA_HIP(fa_launch_group_envs(env_strategy, a.E, pool_size, a.G, a.A, env->grp_env_list, env->grp_tile_strategy,
                                     env->grp_tiles_max, s));
@@ -668,7 +673,7 @@ int fa_policy_act(fa_env *env, const fa_policy_io *io, void *stream) {
     if (!env || !io) return fail(FA_ERR_INVALID, "fa_policy_act: null argument");
     return policy_launch(env, io->obs, io->weights[0], io->weights[1], io->value, io->action, io->log_prob, io->counter,
                          io->seed, io->step, io->deterministic, io->value_only, io->attacker_pool, io->pool_size,
-                         io->env_strategy, stream, "fa_policy_act");
+                         io->env_strategy, io->team_attn, io->opp_attn, stream, "fa_policy_act");
 }
 
 int fa_collect_act(fa_env *env, int32_t step, const fa_policy_io *io, void *stream) {
@@ -683,8 +688,8 @@ int fa_collect_act(fa_env *env, int32_t step, const fa_policy_io *io, void *stre
     return policy_launch(env, st.obs + (size_t)step * EN * FA_OBS_DIM, io->weights[0], io->weights[1],
                          st.value_preds + (size_t)step * EN, value_only ? nullptr : st.actions + (size_t)step * EN,
                          value_only ? nullptr : st.action_log_probs + (size_t)step * EN, io->counter, io->seed, step,
-                         io->deterministic, value_only, io->attacker_pool, io->pool_size, io->env_strategy, stream,
-                         "fa_collect_act");
+                         io->deterministic, value_only, io->attacker_pool, io->pool_size, io->env_strategy, io->team_attn,
+                         io->opp_attn, stream, "fa_collect_act");
 }
 
 int64_t fa_policy_weight_floats(void) { return FA_POLICY_WEIGHT_FLOATS; }

@@ -55,6 +55,10 @@ struct FaPolicyArgs {
     const int32_t *env_list;       // [tiles][ET] env index of every tile slot (-1 = empty), from fa_group_envs_kernel
     const int32_t *tile_strategy;  // [tiles] strategy of the tile's envs (-1 = unused tile)
     int32_t tiles;                 // grid size in tiles when env_list is set
+    // the softmax weights of the forward (policy.attn_mat / opp_attn_mat, mpnn.py:139-140, :158-166), float32, row (e, i) of
+    // team t at ((size_t)e * n + i) * nk: team_attn (E, n, n) = the last message-passing round's, opp_attn (E, n, m).
+    // Any non-null entry selects the exporting instantiation; a null entry among them is not written.
+    float *team_attn[2], *opp_attn[2];
 };
 #define FA_POLICY_MAX_POOL 64 // strategies in an ensemble
 

@@ -104,7 +104,10 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32
     } else if constexpr (NW == 12) {                                                  \
         const int R0 = wave >> 2; constexpr int NR = 1; __VA_ARGS__                   \
     } else { constexpr int R0 = 0, NR = NRB; __VA_ARGS__ }
-template <int NRB, int NW>
+// ATTN = the instantiation that also exports the softmax weights a_ij (the reference's policy.attn_mat / opp_attn_mat,
+// mpnn.py:139-140, :158-166): the 96-row tile without it sits at its register budget, so the export is a kernel of its own,
+// not a run-time branch; `if constexpr (ATTN)` keeps every line of it out of the other one.
+template <int NRB, int NW, bool ATTN>
 __global__ __launch_bounds__(NW * 64, NRB == 2 ? 2 : 1) void fa_policy_kernel(FaPolicyArgs a) {
     static_assert((NRB == 3 && (NW == 8 || NW == 12)) || NW == 4, "eight / twelve waves: the 96-row tile");
     constexpr int PR = 32 * NRB; // rows (env, agent) per tile
@@ -221,13 +224,24 @@ __global__ __launch_bounds__(NW * 64, NRB == 2 ? 2 : 1) void fa_policy_kernel(Fa
     constexpr int AIT = PR / (NW * 4); // attention rows per 16-lane sub-group
     const int q16 = lane & 15, arow0 = wave * 4 + (lane >> 4), RU = ET * n;
     const bool small_teams = (n > m ? n : m) <= 4, mid_teams = (n > m ? n : m) <= 6; // keys held in registers: 4, 6 or 8
+    // ATTN: where row r = (tile slot el, own agent i) of an (E, n, nk) attention matrix lives -- indexed by the env's index
+    // in the handle, sE[el], never by the slot (ensemble tiles are scattered); null for the rows that must not be written:
+    // the clamped recomputations r >= RU and the empty slots of a tile
+    auto attn_dst = [&](float *base, int r, int nk) -> float * {
+        if (!base || r >= RU) return nullptr;
+        const int el = div_n(r), e = sE[el];
+        return e >= 0 ? base + ((size_t)e * n + (r - el * n)) * nk : nullptr;
+    };
     auto opp_attention = [&](auto MTc) __attribute__((always_inline)) {
         constexpr int MT = decltype(MTc)::value;
         float ov[AIT][4];
 #pragma unroll
         for (int k = 0; k < AIT; ++k) {
             const int r = arow0 + k * NW * 4, rr = r < RU ? r : RU - 1;
-            attend_row_regs<64, MT>(sG + rr * LDA + 64, sG + (div_n(rr) * m) * LDA, m, -1, q16, ov[k]);
+            if constexpr (ATTN) // a_ij over the env's opponents, in the opponent team's own order (mpnn.py:409-425)
+                attend_row_regs<64, MT>(sG + rr * LDA + 64, sG + (div_n(rr) * m) * LDA, m, -1, q16, ov[k], attn_dst(a.opp_attn[team], r, m));
+            else
+                attend_row_regs<64, MT>(sG + rr * LDA + 64, sG + (div_n(rr) * m) * LDA, m, -1, q16, ov[k]);
         }
 #pragma unroll
         for (int k = 0; k < AIT; ++k) {
@@ -259,13 +273,16 @@ __global__ __launch_bounds__(NW * 64, NRB == 2 ? 2 : 1) void fa_policy_kernel(Fa
     __syncthreads();
 
     // ---- K = 3 rounds of message passing with shared weights (mpnn.py:155-157) ------------------------------
-    auto team_attention = [&](auto MTc) __attribute__((always_inline)) {
+    auto team_attention = [&](auto MTc, [[maybe_unused]] float *attn_base) __attribute__((always_inline)) {
         constexpr int MT = decltype(MTc)::value;
         float ov[AIT][8];
 #pragma unroll
         for (int k = 0; k < AIT; ++k) {
             const int r = arow0 + k * NW * 4, rr = r < RU ? r : RU - 1, el = div_n(rr);
-            attend_row_regs<128, MT>(sG + rr * LDA, sH + (el * n) * LDA, n, rr - el * n, q16, ov[k]);
+            if constexpr (ATTN) // a_ij over the team-mates, an exact 0 for j == i (mpnn.py:297-298)
+                attend_row_regs<128, MT>(sG + rr * LDA, sH + (el * n) * LDA, n, rr - el * n, q16, ov[k], attn_dst(attn_base, r, n));
+            else
+                attend_row_regs<128, MT>(sG + rr * LDA, sH + (el * n) * LDA, n, rr - el * n, q16, ov[k]);
         }
 #pragma unroll
         for (int k = 0; k < AIT; ++k) {
@@ -288,9 +305,11 @@ _Pragma("unroll")
         __syncthreads();
         FA_PL_TICK(7 + round * 8)
         // team attention, self excluded (mpnn.py:297-298): hmix -> sG rows
-        if (small_teams) team_attention(std::integral_constant<int, 4>{});
-        else if (mid_teams) team_attention(std::integral_constant<int, 6>{});
-        else team_attention(std::integral_constant<int, FA_POLICY_MAX_TEAM>{});
+        // (ATTN: the reference keeps the LAST round's weights, mpnn.py:158-166)
+        float *const tattn = ATTN && round == 2 ? a.team_attn[team] : nullptr;
+        if (small_teams) team_attention(std::integral_constant<int, 4>{}, tattn);
+        else if (mid_teams) team_attention(std::integral_constant<int, 6>{}, tattn);
+        else team_attention(std::integral_constant<int, FA_POLICY_MAX_TEAM>{}, tattn);
         FA_PL_TICK(8 + round * 8)
         __syncthreads();
         FA_PL_TICK(9 + round * 8)
@@ -474,7 +493,12 @@ hipError_t fa_launch_group_envs(const int32_t *env_strategy, int E, int pool_siz
 hipError_t fa_launch_policy(const FaPolicyArgs &a, hipStream_t st) {
     const int ET = fa_policy_tile_envs(a.E, a.G, a.A);
     const int tiles = a.env_list ? a.tiles : (a.E + ET - 1) / ET;
-    if (policy_rows(a.E, a.G, a.A) == 64) hipLaunchKernelGGL((fa_policy_kernel<2, 4>), dim3(tiles, 2), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((fa_policy_kernel<3, FA_POLICY_WAVES>), dim3(tiles, 2), dim3(FA_POLICY_WAVES * 64), 0, st, a);
+    // the exporting instantiation iff any of the four attention matrices is wanted (a null one among them is skipped)
+    const bool attn = a.team_attn[0] || a.team_attn[1] || a.opp_attn[0] || a.opp_attn[1];
+    const bool rows64 = policy_rows(a.E, a.G, a.A) == 64;
+    if (rows64 && !attn) hipLaunchKernelGGL((fa_policy_kernel<2, 4, false>), dim3(tiles, 2), dim3(256), 0, st, a);
+    else if (rows64) hipLaunchKernelGGL((fa_policy_kernel<2, 4, true>), dim3(tiles, 2), dim3(256), 0, st, a);
+    else if (!attn) hipLaunchKernelGGL((fa_policy_kernel<3, FA_POLICY_WAVES, false>), dim3(tiles, 2), dim3(FA_POLICY_WAVES * 64), 0, st, a);
+    else hipLaunchKernelGGL((fa_policy_kernel<3, FA_POLICY_WAVES, true>), dim3(tiles, 2), dim3(FA_POLICY_WAVES * 64), 0, st, a);
     return hipGetLastError();
 }

@@ -271,12 +271,34 @@ class BatchedFortAttack(object):
             io.attacker_pool, io.pool_size, io.env_strategy = _ptr(pool), int(pool.shape[0]), _ptr(env_strategy)
         return io
 
+    def attn_shapes(self):
+        """Shapes of the four attention matrices: ((team_g, opp_g), (team_a, opp_a)) = (E, n, n) / (E, n, m) per team."""
+        E, G, A = self.E, self.G, self.A
+        return (((E, G, G), (E, G, A)), ((E, A, A), (E, A, G)))
+
+    def new_attn_out(self):
+        """Fresh device buffers for policy_act / collect_act(attn_out=...)."""
+        return tuple(tuple(self._new(sh, torch.float32) for sh in pair) for pair in self.attn_shapes())
+
+    def _set_attn(self, io, attn_out):
+        """fa_policy_io.team_attn / opp_attn <- ((team_g, opp_g), (team_a, opp_a)); a None entry is not exported."""
+        assert len(attn_out) == 2 and all(len(pair) == 2 for pair in attn_out), "attn_out: ((team_g, opp_g), (team_a, opp_a))"
+        for t, (pair, shapes) in enumerate(zip(attn_out, self.attn_shapes())):
+            for buf, shape in zip(pair, shapes):
+                assert buf is None or (buf.is_cuda and buf.dtype == torch.float32 and buf.is_contiguous() and
+                                       tuple(buf.shape) == shape), "attn_out: float32 contiguous %s expected" % (shape,)
+            io.team_attn[t], io.opp_attn[t] = _ptr(pair[0]), _ptr(pair[1])
+
     def policy_act(self, obs, w_guards, w_attackers, seed=0, counter=None, step=0, deterministic=False,
-                   value_only=False, out=None, pool=None, env_strategy=None):
+                   value_only=False, out=None, pool=None, env_strategy=None, return_attn=False, attn_out=None):
         """fa_policy_act: both teams' MPNN forward + sampling on an observation row obs (E, N, 6) float32.
         w_*: packed weight buffers (mpnn_pack.pack_policy); with `pool` (K, floats) + `env_strategy` (E) int32
         env e's attackers run strategy env_strategy[e] of the pool.  Returns (value, action, log_prob), each
-        (E, N) (action / log_prob are None with value_only)."""
+        (E, N) (action / log_prob are None with value_only).  return_attn: a fourth value ((team_g, opp_g), (team_a, opp_a)),
+        the attention maps of this forward (policy.attn_mat / opp_attn_mat of the reference, mpnn.py:139-140, :158-166):
+        float32 (E, n, n) -- the last message-passing round's, zero diagonal -- and (E, n, m) per team, written into
+        `attn_out` (same structure) when given.  Asking for them runs the exporting instantiation of the kernel; value,
+        action and log_prob are the same bits either way."""
         assert obs.is_cuda and obs.dtype == torch.float32 and obs.is_contiguous() and tuple(obs.shape) == (self.E, self.N, 6)
         value, action, logp = out if out is not None else (
             self._new((self.E, self.N), torch.float32),
@@ -284,14 +306,22 @@ class BatchedFortAttack(object):
             None if value_only else self._new((self.E, self.N), torch.float32))
         io = self._policy_io(w_guards, w_attackers, seed, counter, step, deterministic, value_only, pool, env_strategy)
         io.obs, io.value, io.action, io.log_prob = _ptr(obs), _ptr(value), _ptr(action), _ptr(logp)
+        if return_attn or attn_out is not None:
+            attn_out = self.new_attn_out() if attn_out is None else attn_out
+            self._set_attn(io, attn_out)
         _lib.check(self._lib.fa_policy_act(self._h, C.byref(io), _stream()), "fa_policy_act")
+        if return_attn:
+            return value, action, logp, attn_out
         return value, action, logp
 
     def collect_act(self, step, w_guards, w_attackers, seed=0, counter=None, deterministic=False, value_only=False,
-                    pool=None, env_strategy=None):
+                    pool=None, env_strategy=None, attn_out=None):
         """fa_collect_act: the policies act on storage.obs[step] and write value_preds / actions /
-        action_log_probs[step] (value_only: only value_preds[step], the V(obs[T]) of wrap_horizon)."""
+        action_log_probs[step] (value_only: only value_preds[step], the V(obs[T]) of wrap_horizon).  attn_out =
+        ((team_g, opp_g), (team_a, opp_a)): the forward's attention maps go there too (see policy_act)."""
         io = self._policy_io(w_guards, w_attackers, seed, counter, step, deterministic, value_only, pool, env_strategy)
+        if attn_out is not None:
+            self._set_attn(io, attn_out)
         _lib.check(self._lib.fa_collect_act(self._h, int(step), C.byref(io), _stream()), "fa_collect_act")
 
     # -- state snapshot ----------------------------------------------------------------
@@ -352,9 +382,12 @@ class BatchedFortAttack(object):
         """fa_step_variant: name of the step kernel a launch of `num_steps` env-steps uses."""
         return self._lib.fa_step_variant(self._h, int(num_steps)).decode()
 
-    def policy_variant(self):
-        """fa_policy_variant: the fa_policy_kernel shape policy_act / collect_act launch (no attacker pool)."""
-        return self._lib.fa_policy_variant(self._h).decode()
+    def policy_variant(self, export_attention=False):
+        """fa_policy_variant: the fa_policy_kernel shape policy_act / collect_act launch (no attacker pool).  The
+        two-parameter name is the instantiation that exports no attention; export_attention=True names the one a call
+        with return_attn / attn_out runs: the same shape with `true` as its third template argument."""
+        name = self._lib.fa_policy_variant(self._h).decode()
+        return name[:-1] + ", true>" if (export_attention and name) else name
 
     def rng_peek(self, e, count):
         out = np.empty(count, np.float64)
@@ -554,16 +587,19 @@ class FortAttackGlobalEnv(object):
         done = bool(self._np_done[0])
         return obs, reward_n, done, {"n": [{} for _ in range(self.n)]}
 
-    def render(self, attn_list=None, mode="human", close=False, size=350, viz_dead=False):
+    def render(self, attn_list=None, mode="human", close=False, size=350, viz_dead=False, viz_attn=True):
         """fortattack.py:368-600.  The pyglet window is out of scope: mode "human"
         stays a no-op returning [] as the reference's trainers expect; mode "rgb_array" returns [frame], the same
-        scene rasterised headlessly from the device state (render.py), lasers for the agents whose last action was 7."""
+        scene rasterised headlessly from the device state (render.py), lasers for the agents whose last action was 7.
+        attn_list = [[team, opp], ...] (Learner.act's second result; BatchedLearner.attn_list_numpy(env=0)): the guards'
+        attention is drawn as the reference draws it (fortattack.py:439-466, :531-546)."""
         if mode != "rgb_array":
             return []
         from .render import render_state
         st = self._eng.get_state()
         shoot = (self._np_act.reshape(1, -1) == 7) if getattr(self, "_stepped", False) else None
-        return [render_state(st, 0, self._eng.G, shoot=shoot, size=size, viz_dead=viz_dead)]
+        return [render_state(st, 0, self._eng.G, shoot=shoot, size=size, viz_dead=viz_dead, attn_list=attn_list,
+                             viz_attn=viz_attn)]
 
     def terminate(self):
         pass

@@ -320,7 +320,8 @@ class BatchedLearner(object):
     def __init__(self, eng, num_steps=128, hidden_dim=128, lr=1e-4, clip_param=0.2, ppo_epoch=4,
                  num_mini_batch=32, value_loss_coef=0.5, entropy_coef=0.01, max_grad_norm=0.5,
                  gamma=0.99, tau=0.95, clipped_value_loss=True, use_graph=False, group=None, policy_backend="auto",
-                 sample_seed=None, update_backend="auto", exchange="torch", reference_sampling=False):
+                 sample_seed=None, update_backend="auto", exchange="torch", reference_sampling=False,
+                 export_attention=False):
         # defaults: arguments.py:22-45
         # policy_backend: "hip" = the fused fa_policy kernel runs the rollout's forwards (hidden_dim 128),
         # "torch" = the PyTorch modules do, "auto" = hip whenever it supports the configuration
@@ -400,6 +401,39 @@ class BatchedLearner(object):
                 fp.fold_pack()
         self.sample_seed = int(torch.initial_seed() if sample_seed is None else sample_seed) & ((1 << 63) - 1)
         self._rollout_counter = torch.zeros(1, dtype=torch.int64, device=self.device)
+        # export_attention: every act also leaves the policies' attention maps (Learner.act's attn_list, learner.py:143-172)
+        # in four persistent buffers -- allocated here, before any capture: the rollout graph's acting launches write them
+        self.export_attention = bool(export_attention)
+        self._attn = None
+        if self.export_attention:
+            self._attn = tuple(tuple(torch.zeros(sh, dtype=torch.float32, device=self.device) for sh in pair)
+                               for pair in (((self.E, self.G, self.G), (self.E, self.G, self.A)),
+                                            ((self.E, self.A, self.A), (self.E, self.A, self.G))))
+
+    # ---- attention maps of the most recent act (learner.py:103-105, :143-172) -------------
+    @property
+    def attn_list(self):
+        """[[team_g, opp_g], [team_a, opp_a]]: device tensors (E, n, n) / (E, n, m) of the most recent act -- the batched
+        form of Learner.act's attn_list = [[policy.attn_mat, policy.opp_attn_mat] per team].  Row = the attending agent,
+        column = team-mate / opponent; with an attacker ensemble the attackers' are those of the strategy each env ran."""
+        if self._attn is None:
+            raise RuntimeError("attn_list needs BatchedLearner(..., export_attention=True)")
+        return [list(pair) for pair in self._attn]
+
+    def attn_list_numpy(self, env=None):
+        """attn_list in the reference's format, numpy, as env.render(attn_list) takes it: for one chosen env (n, n) / (n, m);
+        with env=None all envs, (E, n, n) / (E, n, m), which is (n, n) / (n, m) when E == 1 -- what the reference's
+        squeeze(0).squeeze(0) leaves of its (1, B, n, .) weights (mpnn.py:140, :166)."""
+        out = []
+        for pair in self.attn_list:
+            mats = [m.detach().cpu().numpy() for m in pair]
+            out.append([m[env] if env is not None else (m[0] if m.shape[0] == 1 else m) for m in mats])
+        return out
+
+    @property
+    def team_attn(self):
+        """Learner.team_attn (learner.py:103-105): the guards' team matrix, in attn_list_numpy()'s format."""
+        return self.attn_list_numpy()[0][0]
 
     def close(self):
         """Release what the constructor took from the communication layer: the library's RCCL communicators
@@ -532,8 +566,9 @@ class BatchedLearner(object):
         self.eng.collect_reset()
 
     def _twin(self):
-        """One batched pass for both teams when they have the same size (and no ensemble)."""
-        if self.G != self.A or self.attacker_pool:
+        """One batched pass for both teams when they have the same size (and no ensemble, and no attention export: the
+        matrices come from MPNN.trunk(return_attn=True), the per-team path)."""
+        if self.G != self.A or self.attacker_pool or self.export_attention:
             return None
         if self._twin_net is None:
             self._twin_net = TwinMPNN(self.policies[0], self.policies[1])
@@ -548,7 +583,8 @@ class BatchedLearner(object):
         pool = self._packed_pool if self.attacker_pool else None
         self.eng.collect_act(s, self._packed[0], None if pool is not None else self._packed[1], self.sample_seed,
                              self._rollout_counter, value_only=value_only, pool=pool,
-                             env_strategy=self.attacker_id if pool is not None else None)
+                             env_strategy=self.attacker_id if pool is not None else None,
+                             attn_out=None if value_only else self._attn)   # (V(obs[T]) is no act: attn_list stays act's)
 
     @torch.no_grad()
     def _act_into_storage(self, s):
@@ -567,9 +603,17 @@ class BatchedLearner(object):
         for pol, own_sl, opp_sl in ((self.policies[0], self.team_slices[0], self.team_slices[1]),
                                     (self.policies[1], self.team_slices[1], self.team_slices[0])):
             if pol is self.policies[1] and self.attacker_pool:
+                if self.export_attention:
+                    raise NotImplementedError("export_attention with an attacker ensemble needs the fused policy kernel "
+                                              "(policy_backend='hip'); the PyTorch path does not export the pool's attention")
                 value, action, logp = self._attacker_forward("act", obs[:, own_sl], obs[:, opp_sl])
             else:
                 value, action, logp = pol.act(obs[:, own_sl], obs[:, opp_sl])
+                if self.export_attention:   # the same forward's weights (no sampling involved: deterministic in obs)
+                    t = 0 if pol is self.policies[0] else 1
+                    _, team, opp = pol.trunk(obs[:, own_sl], obs[:, opp_sl], return_attn=True)
+                    self._attn[t][0].copy_(team)
+                    self._attn[t][1].copy_(opp)
             st.value_preds[s, :, own_sl] = value
             st.actions[s, :, own_sl] = action
             st.action_log_probs[s, :, own_sl] = logp

@@ -289,6 +289,21 @@ typedef struct fa_policy_io {
     const float *attacker_pool;  /* device: pool_size packed buffers back to back, or NULL */
     int32_t pool_size;           /* 0 = no ensemble; at most 64 */
     const int32_t *env_strategy; /* device (E): 0..pool_size-1, e.g. the choice_out of fa_set_reset_choice */
+    /* The attention maps of this forward, the reference's policy.attn_mat / policy.opp_attn_mat (mpnn.py:139-140,
+     * :158-166; returned by Learner.act as attn_list and drawn by env.render): device pointers, float32, index 0 =
+     * guards, 1 = attackers, NULL = not wanted (all four NULL: the kernel that does not export them runs, as before
+     * these fields existed).  With n = the team's size and m = the opponents':
+     *   team_attn[t] (E, n, n): the softmax weights of the LAST of the three message-passing rounds.  Row i = the
+     *     attending agent of team t, column j = the team-mate attended to; the diagonal is an exact 0 (an agent does
+     *     not attend to itself, mpnn.py:297-298) and a row sums to 1 -- except for a team of one, whose 1 x 1 matrix is
+     *     0 (mpnn.py:266-274).
+     *   opp_attn[t] (E, n, m): the opponent attention (mpnn.py:409-425).  Row i = the attending agent of team t,
+     *     column j = the opponent, in the opponent team's own order; rows sum to 1.
+     * Env e is the env's index in this handle; with an attacker pool, env e's attacker matrices are those of the
+     * strategy it ran.  Written with value_only and deterministic too.  Not part of the bound storage: fa_collect_act
+     * honours them as fa_policy_act does. */
+    float *team_attn[2];
+    float *opp_attn[2];
 } fa_policy_io;
 int fa_policy_act(fa_env *env, const fa_policy_io *io, void *stream);
 /* The same on the bound storage (io->obs / value / action / log_prob are ignored): reads obs[step], writes
@@ -444,7 +459,9 @@ int fa_selftest_math(fa_env *env, uint64_t samples, uint64_t seed, uint64_t *mis
  * uses on this env (reporting only: bench.py labels its roofline line with it). */
 const char *fa_step_variant(fa_env *env, int32_t num_steps);
 /* which fa_policy_kernel shape fa_policy_act / fa_collect_act launch for this handle:
- * "fa_policy_kernel<3, 8>" (96-row tiles, eight waves) or "fa_policy_kernel<2, 4>" (64-row tiles, four waves: small batches) */
+ * "fa_policy_kernel<3, 8>" (96-row tiles, eight waves) or "fa_policy_kernel<2, 4>" (64-row tiles, four waves: small batches).
+ * The two-parameter spelling names the instantiation that exports no attention; a call with any of fa_policy_io's team_attn /
+ * opp_attn set runs the same shape's exporting one, "fa_policy_kernel<3, 8, true>" / "fa_policy_kernel<2, 4, true>". */
 const char *fa_policy_variant(fa_env *env);
 /* next `count` random_sample() doubles env e would draw (does not advance the stream) */
 int fa_rng_peek(fa_env *env, int32_t e, int32_t count, double *out_host);
