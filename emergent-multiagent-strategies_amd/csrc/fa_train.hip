@@ -252,7 +252,7 @@ __device__ __forceinline__ void fa_train_body(const FaTrainArgs &a) {
     const int n = a.team == 0 ? a.G : a.A, m = N - n;
     const int own0 = a.team == 0 ? 0 : a.G, opp0 = a.team == 0 ? a.G : 0;
     const int ET = TR / (n > m ? n : m);
-    const int tile = blockIdx.x + a.tile0, slot = blockIdx.x + a.rec_tile0;
+    const int tile = blockIdx.x; // also the tile's slot in rec_a / rec_b / rec_g
     const int e0 = tile * ET;
     if (e0 >= a.B) return;
     const int ne = (a.B - e0) < ET ? (a.B - e0) : ET;
@@ -260,8 +260,8 @@ __device__ __forceinline__ void fa_train_body(const FaTrainArgs &a) {
     const float *W = a.w;
     const float4 *Wq = reinterpret_cast<const float4 *>(a.w), *Tq = reinterpret_cast<const float4 *>(a.wt);
     float *mslab = a.mslab + (size_t)tile * FA_MSLAB_FLOATS;
-    float *recA = a.rec_a + (size_t)slot * 3 * FA_RECA_FLOATS, *recB = a.rec_b + (size_t)slot * FA_RECB_FLOATS;
-    float *recG = a.rec_g + (size_t)slot * 3 * FA_REC_PLANE;
+    float *recA = a.rec_a + (size_t)tile * 3 * FA_RECA_FLOATS, *recB = a.rec_b + (size_t)tile * FA_RECB_FLOATS;
+    float *recG = a.rec_g + (size_t)tile * 3 * FA_REC_PLANE;
 
     // dense tile <-> LDS: W floats per row (128: four 16-byte pieces per thread; 64: two)
     auto save_tile = [&](const float *src, float *dst) { // 32 x 128 LDS -> global
@@ -270,11 +270,7 @@ __device__ __forceinline__ void fa_train_body(const FaTrainArgs &a) {
             const int r = k >> 5, c4 = k & 31;
             // (non-temporal: a record is read once, by another kernel -- it need not displace the weights in L2)
             typedef float v4f __attribute__((ext_vector_type(4)));
-#if FA_REC_NT
             __builtin_nontemporal_store(*reinterpret_cast<const v4f *>(src + r * LDA + c4 * 4), reinterpret_cast<v4f *>(dst) + k);
-#else
-            reinterpret_cast<v4f *>(dst)[k] = *reinterpret_cast<const v4f *>(src + r * LDA + c4 * 4);
-#endif
         }
     };
     auto save_tile64 = [&](const float *src, float *dst) { // 32 x 64 LDS (at src, row stride LDA) -> global
@@ -780,7 +776,7 @@ template <bool GATHER, int MT>
 __global__ __launch_bounds__(NTH, 2) void fa_train_kernel(FaTrainArgs a) { fa_train_body<GATHER, MT>(a); }
 // (Rounds 2-3 had a second, register-capped build for the two teams' concurrent update chains -- it left room on a CU for
 //  the other chain's small launches.  With two 4-wave workgroups per CU the capped build spills more than the sharing
-//  gains: 0.229 s per update capped, 0.207 s uncapped.  FaTrainArgs::share_cu is accepted and ignored.)
+//  gains: 0.229 s per update capped, 0.207 s uncapped.  The public io structure still carries the switch, ignored.)
 
 // The alive-mask sum of the minibatch's own-team rows as FA_MASK_PARTS partial sums (one workgroup each; the
 // train kernel's workgroups fold them in a fixed order: reproducible, and no single-workgroup latency chain)
@@ -841,7 +837,7 @@ int fa_train_tile_envs(int G, int A) { return TR / (G > A ? G : A); }
 
 hipError_t fa_launch_train(const FaTrainArgs &a, hipStream_t st) {
     const int ET = fa_train_tile_envs(a.G, a.A);
-    const dim3 grid(a.ntiles > 0 ? a.ntiles : (a.B + ET - 1) / ET), block(NTH);
+    const dim3 grid((a.B + ET - 1) / ET), block(NTH);
     const int big = a.G > a.A ? a.G : a.A;
 #define FA_TRAIN_LAUNCH(MT)                                                                                   \
     do {                                                                                                      \

@@ -66,15 +66,20 @@ class LibraryExchange(object):
         self.comm = comm
         self._gather = None
 
+    def _buffers(self, eng):
+        """The all-gather / result buffers for `eng`'s agents, remade whenever (world, N) is not what they were made for."""
+        if self._gather is None or tuple(self._gather.shape[:2]) != (self.world, eng.N):
+            f64 = dict(dtype=torch.float64, device=eng.device)
+            self._gather = torch.zeros((self.world, eng.N, 3), **f64)
+            self._mom = torch.zeros((eng.N, 3), **f64)
+            self._mean, self._std = torch.zeros(eng.N, **f64), torch.zeros(eng.N, **f64)
+
     def ranks(self):
         return int(self._L.load().fa_rccl_comm_ranks(self.comm))
 
     def adv_mean_std(self, eng, moments):
         """ppo.py:121-123 over all ranks from this rank's (N,3) moments: fa_adv_allreduce on the current stream."""
-        if self._gather is None:
-            self._gather = torch.zeros((self.world, eng.N, 3), dtype=torch.float64, device=eng.device)
-            self._mean = torch.zeros(eng.N, dtype=torch.float64, device=eng.device)
-            self._std = torch.zeros(eng.N, dtype=torch.float64, device=eng.device)
+        self._buffers(eng)
         L = self._L
         L.check(L.load().fa_adv_allreduce(eng._h, moments.data_ptr(), self._gather.data_ptr(), self.comm, self._mean.data_ptr(),
                                           self._std.data_ptr(), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
@@ -86,12 +91,7 @@ class LibraryExchange(object):
         (fa_gae_allreduce_normalize: GAE scan + this rank's moments, the all-gather, merge + normalisation): what
         bench.py --gpus N enqueues per rollout -- no Python between the four device operations, capturable in a hipGraph.
         Returns (adv (T, E, N, 1) float32, mean (N,), std (N,)) over ALL ranks' samples."""
-        if self._gather is None:
-            self._gather = torch.zeros((self.world, eng.N, 3), dtype=torch.float64, device=eng.device)
-            self._mean = torch.zeros(eng.N, dtype=torch.float64, device=eng.device)
-            self._std = torch.zeros(eng.N, dtype=torch.float64, device=eng.device)
-        if getattr(self, "_mom", None) is None:
-            self._mom = torch.zeros((eng.N, 3), dtype=torch.float64, device=eng.device)
+        self._buffers(eng)
         if out is None:
             out = torch.empty((eng.storage.num_steps, eng.E, eng.N, 1), dtype=torch.float32, device=eng.device)
         L = self._L
@@ -115,6 +115,25 @@ class LibraryExchange(object):
             torch.cuda.synchronize(self.device)
             self._L.load().fa_rccl_comm_destroy(self.comm)
             self.comm = None
+
+
+class TorchExchange(object):
+    """The torch.distributed route behind the two members of LibraryExchange that an optimizer step uses."""
+
+    def __init__(self, group=None):
+        self.group, self.world = group, world_size(group)
+
+    def all_reduce_(self, flat):
+        dist.all_reduce(flat, group=self.group)
+        return flat
+
+
+def exchange_route(group=None, exchange=None):
+    """What carries an optimizer step's gradient exchange: the LibraryExchange passed in, else torch.distributed on `group`
+    when it runs collectives (exchanging(group)), else None: one rank, nothing to exchange."""
+    if exchange is not None:
+        return exchange
+    return TorchExchange(group) if exchanging(group) else None
 
 
 def _all_reduce_sum_(t, group=None):

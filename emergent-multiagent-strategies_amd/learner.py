@@ -66,21 +66,128 @@ def _capture_mode():
     return "thread_local" if (dist.is_available() and dist.is_initialized()) else "global"
 
 
-def _world(group=None):
-    return dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
+def finish_exchange_(flat, n, world):
+    """The arithmetic behind an optimizer step's all-reduce, in place on the summed flat buffer
+    [gradients (n floats) | 3 loss sums | alive-mask mean | ...]: the mean over the ranks (equal shard sizes: == the union
+    mean), then the division by the all-rank mask mean (1 where that is 0) that the ranks left out (ppo_losses
+    normalize=False).  n = the packed gradients' length (autograd) or mpnn_pack.PF_FLOATS (FlatPolicy.gflat).
+    Returns the three losses as a view of flat."""
+    flat.div_(world)
+    mm = flat[n + 3]
+    flat.div_(torch.where(mm != 0, mm, torch.ones_like(mm)))
+    return flat[n:n + 3]
 
 
-class GraphedPPOStep(object):
-    """One optimizer step of joint_ppo_update -- minibatch forward, backward, (gradient exchange,) clip, Adam --
-    captured as hipGraph(s) and replayed with a new minibatch index set.
+class PPOStep(object):
+    """One optimizer step of joint_ppo_update -- minibatch forward, backward, (gradient exchange,) clip, optimizer -- as
+    fwd_bwd / all-reduce / finish, run as it stands by eager() (any device, any torch.optim optimizer) or captured by
+    GraphedPPOStep.
 
-    `fused` (csrc/fa_train.hip, fa_fold.hip): fold the parameters into weight packs, fa_ppo_grad on rows
-    idx of the rollout read in place (forward + losses + backward in one launch), unfold the gradients, fa_adam_step
-    on the flat parameter / gradient / moment buffers of mpnn_pack.FlatPolicy: ~16 graph nodes, no autograd.
-    `share_cu`: the build of the kernel that leaves room on its CUs (two teams updated concurrently).
-    Otherwise PyTorch autograd on a minibatch gathered into static buffers (index_select, outside the graph): ~300
-    small kernels whose Python / dispatcher time (4 ms) exceeded their GPU time (2.7 ms at 16 384 x 3 samples)
-    before they were replayed from a graph.
+    The forward + backward is PyTorch autograd on a gathered minibatch, or -- after use_fused_kernel() -- the fused kernel
+    (csrc/fa_train.hip, fa_fold.hip): fold the parameters into weight packs, fa_ppo_grad on rows idx of the
+    rollout read in place (forward + losses + backward in one launch), unfold the gradients, fa_adam_step on the flat
+    parameter / gradient / moment buffers of mpnn_pack.FlatPolicy: ~16 graph nodes, no autograd.
+
+    The gradient exchange: `exchange` (dist.LibraryExchange: RCCL inside the library) or torch.distributed on `group`; a
+    world of one rank exchanges nothing unless dist.FORCE_COLLECTIVE / an explicit exchange says so.
+    adv_stats (fused only): persistent (mean, std) float64 (N,) device tensors -> the kernel normalises the advantages
+    itself from returns - value_preds (ppo.py:121-124) and rows[5] is never read."""
+    fused = False
+
+    def __init__(self, pol, opt, own_sl, opp_sl, clip_param, value_loss_coef, entropy_coef, max_grad_norm,
+                 clipped_value_loss, group=None, exchange=None, adv_stats=None):
+        self.pol, self.opt, self.own_sl, self.opp_sl = pol, opt, own_sl, opp_sl
+        self.clip_param, self.value_loss_coef, self.entropy_coef = clip_param, value_loss_coef, entropy_coef
+        self.max_grad_norm, self.clipped_value_loss = max_grad_norm, clipped_value_loss
+        self.route = fa_dist.exchange_route(group, exchange)
+        self.world = self.route.world if self.route is not None else 1
+        self.adv_stats = adv_stats
+        self.params = [p for p in pol.parameters()]
+
+    def use_fused_kernel(self, rows, mb):
+        """csrc/fa_train.hip: forward + losses + backward of minibatch self.idx (mb rows of `rows`) in one launch"""
+        dev = rows[0].device
+        self.fused = True
+        self.rows = tuple(rows)
+        self.fp = mpnn_pack.FlatPolicy.of(self.pol)
+        self.fp.bind_adam(self.opt)
+        self.idx = torch.zeros(mb, dtype=torch.int64, device=dev)
+        self._out = torch.zeros(mpnn_pack.SLAB_FLOATS, device=dev)
+        self._scratch = None
+        self._inv_count = 1.0 / (mb * (self.own_sl.stop - self.own_sl.start))
+        self._unmask = torch.tensor([0.0, 1.0, 1.0], device=dev)
+
+    def fused_fwd_bwd(self):
+        """parameters -> weight packs (fold: 3 launches) -> fa_ppo_grad on rows idx of the rollout (mask mean,
+        forward + losses + backward, reduction: 3) -> gradients of the parameters (unfold: 2): no PyTorch
+        autograd, GEMM or gather; left to torch are four scalar ops on the loss sums"""
+        from .env import ppo_grad
+        fp, rows = self.fp, self.rows
+        PF, LOSS = mpnn_pack.PF_FLOATS, mpnn_pack.PLAIN_FLOATS
+        N, n_own = rows[0].shape[1], self.own_sl.stop - self.own_sl.start
+        team, G = (0, n_own) if self.own_sl.start == 0 else (1, N - n_own)
+        w, wt = fp.fold_pack()
+        _, self._scratch = ppo_grad(*rows[:5], None if self.adv_stats is not None else rows[5], w, wt, None, team, G, N - G,
+                                    self.clip_param, self.value_loss_coef, self.entropy_coef, self.clipped_value_loss,
+                                    scratch=self._scratch, out=self._out, idx=self.idx, normalize=self.route is None,
+                                    adv_stats=self.adv_stats)
+        fp.attach_grads()               # every parameter's .grad is its slice of fp.gflat
+        fp.unfold(self._out)
+        sums = self._out[LOSS:LOSS + 3] * self._inv_count
+        mmp = self._out[LOSS + 9]       # the alive-mask mean of the minibatch (1 where that is 0)
+        if not self.clipped_value_loss:  # the scalar-MSE value loss is not masked (ppo.py:178-182)
+            sums = sums * (self._unmask + (1.0 - self._unmask) * mmp)
+        if self.route is None:
+            return sums / mmp, None
+        fp.gflat[PF:PF + 3].copy_(sums)  # the flat gradient buffer carries the loss sums and the mask mean
+        fp.gflat[PF + 3].copy_(self._out[LOSS + 3] * self._inv_count)
+        return sums, fp.gflat
+
+    def fwd_bwd(self, mb_rows=None):
+        """-> (losses (3,), flat): flat = [gradients | 3 loss sums | alive-mask mean] to all-reduce, None without an
+        exchange.  mb_rows: the six gathered minibatch tensors (autograd; the fused kernel gathers rows self.idx itself)."""
+        if self.fused:
+            return self.fused_fwd_bwd()
+        own_sl, opp_sl = self.own_sl, self.opp_sl
+        obs_b, act_b, vp_b, ret_b, olp_b, adv_b = mb_rows
+        out = ppo_losses(self.pol, obs_b[:, own_sl], obs_b[:, opp_sl], act_b[:, own_sl], vp_b[:, own_sl], ret_b[:, own_sl],
+                         olp_b[:, own_sl], adv_b[:, own_sl], self.clip_param, self.clipped_value_loss,
+                         normalize=self.route is None)
+        self.opt.zero_grad(set_to_none=True)
+        (out[0] * self.value_loss_coef + out[1] - out[2] * self.entropy_coef).backward()
+        losses = torch.stack([out[0].detach(), out[1].detach(), out[2].detach()])
+        if self.route is None:
+            return losses, None
+        grads = [p.grad for p in self.params if p.grad is not None]
+        return losses, torch.cat([g.reshape(-1) for g in grads] + [losses, out[3].detach().reshape(1)])
+
+    def finish(self, losses, flat):
+        """flat: after the all-reduce (sum over ranks).  -> the step's three losses"""
+        if flat is not None:
+            losses = finish_exchange_(flat, mpnn_pack.PF_FLOATS if self.fused else flat.numel() - 4, self.world)
+            off = 0
+            for g in [] if self.fused else [p.grad for p in self.params if p.grad is not None]:   # (fused: flat IS fp.gflat)
+                g.copy_(flat[off:off + g.numel()].view_as(g))
+                off += g.numel()
+        if self.fused:      # parameters, gradients and Adam state are flat buffers: clip + Adam = 2 launches
+            self.fp.adam_step(self.opt, self.max_grad_norm)
+        else:
+            nn.utils.clip_grad_norm_(self.params, self.max_grad_norm)
+            self.opt.step()
+        return losses.clone()
+
+    def eager(self, mb_rows=None):
+        losses, flat = self.fwd_bwd(mb_rows)
+        if flat is not None:
+            self.route.all_reduce_(flat)
+        return self.finish(losses, flat)
+
+
+class GraphedPPOStep(PPOStep):
+    """A PPOStep captured as hipGraph(s) and replayed with a new minibatch index set.  `fused`: the fa_ppo_grad kernel
+    reads rows idx of the rollout in place.  Otherwise PyTorch autograd on a minibatch gathered into static buffers
+    (index_select, outside the graph): ~300 small kernels whose Python / dispatcher time (4 ms) exceeded their GPU time
+    (2.7 ms at 16 384 x 3 samples) before they were replayed from a graph.
 
     Parameters, gradients and Adam state are the live tensors (the optimizer must be `capturable`).  One rank: one
     graph.  Several ranks: two graphs around the eager all-reduce of the flat buffer (see joint_ppo_update).
@@ -88,102 +195,16 @@ class GraphedPPOStep(object):
     restored) before the first real step."""
 
     def __init__(self, pol, opt, own_sl, opp_sl, rows, mb, clip_param, value_loss_coef, entropy_coef, max_grad_norm,
-                 clipped_value_loss, group, fused=False, share_cu=False, exchange=None, adv_stats=None):
-        # adv_stats (fused only): persistent (mean, std) float64 (N,) device tensors -> the kernel normalises the advantages
-        # itself from returns - value_preds (ppo.py:121-124) and rows[5] is never read
-        # the gradient exchange: `exchange` (dist.LibraryExchange: RCCL inside the library) or torch.distributed on
-        # `group`; a world of one rank exchanges nothing unless dist.FORCE_COLLECTIVE / an explicit exchange says so
-        self.pol, self.opt, self.group = pol, opt, group
-        self.world = exchange.world if exchange is not None else _world(group)
-        self.exchanging = exchange is not None or fa_dist.exchanging(group)
-        self._reduce = exchange.all_reduce_ if exchange is not None else (lambda t: dist.all_reduce(t, group=group))
-        self.params = [p for p in pol.parameters()]
-        self.fused = bool(fused)
-        self.max_grad_norm = max_grad_norm
+                 clipped_value_loss, group, fused=False, exchange=None, adv_stats=None):
+        super().__init__(pol, opt, own_sl, opp_sl, clip_param, value_loss_coef, entropy_coef, max_grad_norm,
+                         clipped_value_loss, group, exchange, adv_stats)
+        self.rows, self.mb = tuple(rows), mb
         # torch path: the minibatch is gathered into static buffers; fused: the kernel reads rows idx of the rollout
-        self.static = None if self.fused else [torch.empty((mb,) + tuple(r.shape[1:]), dtype=r.dtype, device=r.device) for r in rows]
-        self.rows = tuple(rows)
-        self.mb = mb
-        world, exchanging = self.world, self.exchanging
-        if self.fused:   # csrc/fa_train.hip: forward + losses + backward of the minibatch in one launch
-            from .env import ppo_grad
-            dev = rows[0].device
-            N = rows[0].shape[1]
-            n_own = own_sl.stop - own_sl.start
-            team, G = (0, n_own) if own_sl.start == 0 else (1, N - n_own)
-            self.fp = mpnn_pack.FlatPolicy.of(pol)
-            self.fp.bind_adam(opt)
-            self.idx = torch.zeros(mb, dtype=torch.int64, device=dev)
-            self._out = torch.zeros(mpnn_pack.SLAB_FLOATS, device=dev)
-            self._scratch = None
-            inv_count = 1.0 / (mb * n_own)
-            PF, LOSS = mpnn_pack.PF_FLOATS, mpnn_pack.PLAIN_FLOATS
-            self._unmask = torch.tensor([0.0, 1.0, 1.0], device=dev)
-
-        def fused_fwd_bwd():
-            """parameters -> weight packs (fold: 3 launches) -> fa_ppo_grad on rows idx of the rollout (mask mean,
-            forward + losses + backward, reduction: 3) -> gradients of the parameters (unfold: 2): no PyTorch
-            autograd, GEMM or gather; left to torch are four scalar ops on the loss sums"""
-            fp = self.fp
-            w, wt = fp.fold_pack()
-            _, self._scratch = ppo_grad(*self.rows[:5], None if adv_stats is not None else self.rows[5], w, wt, None, team, G, N - G,
-                                        clip_param, value_loss_coef, entropy_coef, clipped_value_loss, scratch=self._scratch,
-                                        out=self._out, idx=self.idx, normalize=not exchanging, share_cu=share_cu, adv_stats=adv_stats)
-            fp.attach_grads()               # every parameter's .grad is its slice of fp.gflat
-            fp.unfold(self._out)
-            sums = self._out[LOSS:LOSS + 3] * inv_count
-            mmp = self._out[LOSS + 9]       # the alive-mask mean of the minibatch (1 where that is 0)
-            if not clipped_value_loss:      # the scalar-MSE value loss is not masked (ppo.py:178-182)
-                sums = sums * (self._unmask + (1.0 - self._unmask) * mmp)
-            if not exchanging:
-                return sums / mmp, None
-            fp.gflat[PF:PF + 3].copy_(sums)  # the flat gradient buffer carries the loss sums and the mask mean
-            fp.gflat[PF + 3].copy_(self._out[LOSS + 3] * inv_count)
-            return sums, fp.gflat
-
-        def fwd_bwd():
-            if self.fused:
-                return fused_fwd_bwd()
-            obs_b, act_b, vp_b, ret_b, olp_b, adv_b = self.static
-            out = ppo_losses(pol, obs_b[:, own_sl], obs_b[:, opp_sl], act_b[:, own_sl], vp_b[:, own_sl], ret_b[:, own_sl],
-                             olp_b[:, own_sl], adv_b[:, own_sl], clip_param, clipped_value_loss, normalize=not exchanging)
-            opt.zero_grad(set_to_none=True)
-            (out[0] * value_loss_coef + out[1] - out[2] * entropy_coef).backward()
-            losses = torch.stack([out[0].detach(), out[1].detach(), out[2].detach()])
-            if not exchanging:
-                return losses, None
-            grads = [p.grad for p in self.params if p.grad is not None]
-            return losses, torch.cat([g.reshape(-1) for g in grads] + [losses, out[3].detach().reshape(1)])
-
-        def finish(losses, flat):
-            if flat is not None and self.fused:               # in place: flat IS the gradients (fp.gflat)
-                flat.div_(world)
-                mm = flat[PF + 3].clone()
-                flat.div_(torch.where(mm != 0, mm, torch.ones_like(mm)))
-                losses = flat[PF:PF + 3]
-            elif flat is not None:                            # after the all-reduce (sum over ranks)
-                flat = flat / world
-                mm = flat[-1]
-                flat = flat / torch.where(mm != 0, mm, torch.ones_like(mm))
-                losses = flat[-4:-1]
-                off = 0
-                for p in self.params:
-                    if p.grad is not None:
-                        p.grad.copy_(flat[off:off + p.grad.numel()].view_as(p.grad))
-                        off += p.grad.numel()
-            if self.fused:      # parameters, gradients and Adam state are flat buffers: clip + Adam = 2 launches
-                self.fp.adam_step(opt, max_grad_norm)
-            else:
-                nn.utils.clip_grad_norm_(self.params, max_grad_norm)
-                opt.step()
-            return losses.clone()
-
-        def eager():
-            losses, flat = fwd_bwd()
-            if flat is not None:
-                self._reduce(flat)
-            return finish(losses, flat)
-
+        self.static = None
+        if fused:
+            self.use_fused_kernel(rows, mb)
+        else:
+            self.static = [torch.empty((mb,) + tuple(r.shape[1:]), dtype=r.dtype, device=r.device) for r in rows]
         # ---- warm-up on a side stream, then undo it -------------------------------------------------------
         if self.fused:
             self.idx.copy_(torch.arange(mb, device=rows[0].device))
@@ -197,7 +218,7 @@ class GraphedPPOStep(object):
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(3):
-                eager()
+                self.eager(self.static)
         torch.cuda.current_stream().wait_stream(side)
         with torch.no_grad():
             for p, q in zip(self.params, saved_p):
@@ -209,15 +230,15 @@ class GraphedPPOStep(object):
         # ---- capture -----------------------------------------------------------------------------------
         self.g1 = torch.cuda.CUDAGraph()
         self.g2 = None
-        if not exchanging:
+        if self.route is None:
             with torch.cuda.graph(self.g1, capture_error_mode=_capture_mode()):
-                self.losses = eager()
+                self.losses = self.eager(self.static)
         else:
             with torch.cuda.graph(self.g1, capture_error_mode=_capture_mode()):
-                l0, self.flat = fwd_bwd()
+                l0, self.flat = self.fwd_bwd(self.static)
             self.g2 = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.g2, pool=self.g1.pool(), capture_error_mode=_capture_mode()):
-                self.losses = finish(l0, self.flat)
+                self.losses = self.finish(l0, self.flat)
 
     def run(self, rows, idx, reduce_after=None, reduce_done=None):
         """reduce_after / reduce_done: events that order this step's collective against another chain's on the same
@@ -233,7 +254,7 @@ class GraphedPPOStep(object):
         if self.g2 is not None:
             if reduce_after is not None:
                 torch.cuda.current_stream().wait_event(reduce_after)
-            self._reduce(self.flat)          # between the two graphs, on the same stream
+            self.route.all_reduce_(self.flat)          # between the two graphs, on the same stream
             if reduce_done is not None:
                 reduce_done.record()
             self.g2.replay()
@@ -261,15 +282,15 @@ def joint_ppo_update(pol, opt, own_sl, opp_sl, rows, clip_param, ppo_epoch, num_
     CUDA tensors and a capturable optimizer); a ragged last minibatch runs eagerly.
     Returns a (3,) tensor: (value_loss, action_loss, entropy) summed over the minibatches and divided by
     ppo_epoch * num_mini_batch as the reference does (ppo.py:196-200)."""
-    obs_f, act_f, vp_f, ret_f, olp_f, adv_f = rows
+    obs_f = rows[0]
     batch = obs_f.shape[0]
     assert batch >= num_mini_batch, (
         "PPO requires the number of processes * number of steps = {} to be greater than "
         "or equal to the number of PPO mini batches ({}).".format(batch, num_mini_batch))
     mb = int(batch / num_mini_batch)                             # ppo.py:210
-    world = exchange.world if exchange is not None else _world(group)
-    exchanging = exchange is not None or fa_dist.exchanging(group)
-    params = [p for p in pol.parameters()]
+    # what no captured step runs -- the ragged last minibatch, or every minibatch without `graphs` -- runs this step eagerly
+    step = PPOStep(pol, opt, own_sl, opp_sl, clip_param, value_loss_coef, entropy_coef, max_grad_norm, clipped_value_loss,
+                   group, exchange, adv_stats)
     acc = torch.zeros(3, device=obs_f.device)
     for epoch in range(ppo_epoch):
         if sampler is not None:
@@ -286,33 +307,8 @@ def joint_ppo_update(pol, opt, own_sl, opp_sl, rows, clip_param, ppo_epoch, num_
                                                  fused=graphs.get("fused", False) and mpnn_pack.supported(pol),
                                                  exchange=exchange, adv_stats=adv_stats)
                 acc += graphs[key].run(rows, idx)
-                continue
-            obs_b = obs_f[idx]
-            out = ppo_losses(pol, obs_b[:, own_sl], obs_b[:, opp_sl], act_f[idx][:, own_sl], vp_f[idx][:, own_sl],
-                             ret_f[idx][:, own_sl], olp_f[idx][:, own_sl], adv_f[idx][:, own_sl], clip_param,
-                             clipped_value_loss, normalize=not exchanging)
-            value_loss, action_loss, dist_entropy = out[:3]
-            opt.zero_grad(set_to_none=True)
-            (value_loss * value_loss_coef + action_loss - dist_entropy * entropy_coef).backward()
-            losses = torch.stack([value_loss.detach(), action_loss.detach(), dist_entropy.detach()])
-            if exchanging:
-                grads = [p.grad for p in params if p.grad is not None]
-                flat = torch.cat([g.reshape(-1) for g in grads] + [losses, out[3].detach().reshape(1)])
-                if exchange is not None:
-                    exchange.all_reduce_(flat)
-                else:
-                    dist.all_reduce(flat, group=group)
-                flat.div_(world)                                 # equal shard sizes: mean over ranks == union mean
-                mm = flat[-1]
-                flat.div_(torch.where(mm != 0, mm, torch.ones_like(mm)))
-                losses = flat[-4:-1]
-                off = 0
-                for g in grads:
-                    g.copy_(flat[off:off + g.numel()].view_as(g))
-                    off += g.numel()
-            nn.utils.clip_grad_norm_(params, max_grad_norm)
-            opt.step()
-            acc += losses
+            else:
+                acc += step.eager([r[idx] for r in rows])
     return acc / (ppo_epoch * num_mini_batch)                    # ppo.py:196-200 (not the batches actually drawn)
 
 
@@ -730,11 +726,7 @@ class BatchedLearner(object):
         # The fused optimizer steps normalise the advantages inside the kernel from (mean, std): the (T, E, N) advantage
         # tensor is only materialised for the paths that read it (PyTorch autograd, a caller's sampler, a ragged last
         # minibatch that runs eagerly)
-        batch = T * E
-        mb = int(batch / self.num_mini_batch) if batch >= self.num_mini_batch else 0
-        g = self._update_graphs
-        in_kernel = (g is not None and g.get("fused", False) and (sampler is None or graphs_with_sampler) and mb > 0
-                     and batch % mb == 0 and all(mpnn_pack.supported(p) for p in self.policies))
+        in_kernel = (sampler is None or graphs_with_sampler) and self._fused_steps_ok(T * E)
         adv_stats = (self._adv_mean, self._adv_std) if in_kernel else None
         if not in_kernel:
             self.eng.adv_normalize(mean, std, out=self.adv)      # ppo.py:123
@@ -743,7 +735,7 @@ class BatchedLearner(object):
                 flat(st.action_log_probs), flat(self.adv))
         out = []
         teams = [0] if train_guards_only else [0, 1]             # learner.py:177
-        if len(teams) == 2 and sampler is None and self._teams_step_ok(rows):
+        if len(teams) == 2 and sampler is None and in_kernel and self._update_graphs.get("teams_together", True):
             return self._update_teams_together(rows, adv_stats)
         for ti in teams:
             out.append(joint_ppo_update(
@@ -766,12 +758,13 @@ class BatchedLearner(object):
             return [perm[k:k + mb].to(dev) for k in range(0, batch, mb)]
         return sampler
 
-    def _teams_step_ok(self, rows):
+    def _fused_steps_ok(self, batch):
+        """Whether every optimizer step of an update over `batch` rows is the captured fused step: the fused backend on
+        policies it supports and no ragged last minibatch."""
         g = self._update_graphs
-        batch = rows[0].shape[0]
         mb = int(batch / self.num_mini_batch) if batch >= self.num_mini_batch else 0
-        return (g is not None and g.get("fused", False) and g.get("teams_together", True)
-                and mb > 0 and batch % mb == 0 and all(mpnn_pack.supported(p) for p in self.policies))
+        return (g is not None and g.get("fused", False) and mb > 0 and batch % mb == 0
+                and all(mpnn_pack.supported(p) for p in self.policies))
 
     def _update_teams_together(self, rows, adv_stats=None):
         """Both teams' JointPPO.update (learner.py:175-188 runs them one after the other; they share nothing but the
@@ -784,11 +777,11 @@ class BatchedLearner(object):
         perms = [[torch.randperm(batch, device=dev) for _ in range(self.ppo_epoch)] for _ in range(2)]
         steps = []
         for ti in range(2):
-            key = (id(self.policies[ti]), mb, "shared")     # (the build of fa_train_kernel that leaves room on its CUs)
+            key = (id(self.policies[ti]), mb, "shared")     # (its own captured step: the two chains replay concurrently)
             if key not in g:
                 g[key] = GraphedPPOStep(self.policies[ti], self.optimizers[ti], self.team_slices[ti], self.team_slices[1 - ti],
                                         rows, mb, self.clip_param, self.value_loss_coef, self.entropy_coef, self.max_grad_norm,
-                                        self.clipped_value_loss, self._team_groups[ti], fused=True, share_cu=g.get("share_cu", True),
+                                        self.clipped_value_loss, self._team_groups[ti], fused=True,
                                         exchange=self._team_exch[ti], adv_stats=adv_stats)
             steps.append(g[key])
             assert all(a.data_ptr() == b.data_ptr() for a, b in zip(rows, g[key].rows)), "the captured step reads the rollout in place"

@@ -216,3 +216,28 @@ def test_pin_rank_record_and_restore():
         assert rec["source"].startswith("allowed-split") or rec["source"].startswith("numa-local")
     finally:
         os.sched_setaffinity(0, before)
+
+
+def test_library_exchange_buffers_follow_the_engine_they_are_used_with():
+    """LibraryExchange._buffers: the all-gather / moment / result buffers are made for (world, eng.N) and remade when a later
+    engine has another N (they were sized once, from the first engine: a larger N wrote past them); unchanged N keeps them --
+    captured graphs point at them."""
+    from emergent_multiagent_strategies_amd.dist import LibraryExchange
+
+    class Eng(object):
+        device = torch.device("cpu")
+
+        def __init__(self, N):
+            self.N = N
+
+    ex = object.__new__(LibraryExchange)
+    ex.world, ex._gather = 2, None
+    ex._buffers(Eng(6))
+    first = ex._gather
+    assert tuple(first.shape) == (2, 6, 3) and tuple(ex._mom.shape) == (6, 3) and ex._mean.shape == ex._std.shape == (6,)
+    ex._buffers(Eng(6))
+    assert ex._gather is first
+    ex._buffers(Eng(10))
+    assert tuple(ex._gather.shape) == (2, 10, 3) and tuple(ex._mom.shape) == (10, 3)
+    assert ex._mean.shape == ex._std.shape == (10,)
+    assert all(t.dtype == torch.float64 for t in (ex._gather, ex._mom, ex._mean, ex._std))

@@ -463,3 +463,33 @@ def test_reference_sampling_mode_replays_the_cpu_generator(fa):
     assert torch.equal(l0, l1) and all(torch.equal(a, b) for a, b in zip(p0, p1))
     assert (l0 - l2).abs().max() < 2e-4 * max(1.0, float(l0.abs().max()))
     assert max(float((x - y).abs().max()) for x, y in zip(p0, p2)) < 4e-4   # 8 Adam steps of 1e-4
+
+
+def test_update_with_a_ragged_last_minibatch_mixes_captured_and_eager_steps(fa):
+    """batch 528 = 66 envs x 8 steps in 5 minibatches: mb = 105, so every epoch of a team is five full minibatches (replayed
+    from the captured step with use_graph) and one of 3 rows, which always runs as the eager step.  The PyTorch-autograd
+    update with use_graph=True (captured + eager steps mixed) against use_graph=False (every step eager) from the same
+    rollout, policies and minibatch index sets: the two run the same PyTorch operators on the same values -- measured
+    before the step implementations were merged: parameters and losses identical bit for bit -- so equality is asserted."""
+    res = []
+    for use_graph in (True, False):
+        torch.manual_seed(11)
+        eng = fa.BatchedFortAttack(66, 3, 3, 12, base_seed=3)
+        L = fa.BatchedLearner(eng, num_steps=8, num_mini_batch=5, ppo_epoch=2, use_graph=use_graph, update_backend="torch",
+                              reference_sampling=True)
+        L.reset()
+        L.collect()
+        torch.manual_seed(23)                       # the minibatch permutations (CPU generator: reference_sampling)
+        losses = L.update()
+        torch.cuda.synchronize()
+        if use_graph:
+            assert any(isinstance(k, tuple) for k in L._update_graphs)      # the full minibatches replayed captured steps
+        res.append((losses.cpu(), [p.detach().cpu().clone() for pol in L.policies for p in pol.parameters()],
+                    L.storage.actions.clone()))
+    (l0, p0, a0), (l1, p1, a1) = res
+    assert torch.equal(a0, a1)                      # same rollout
+    worst = max(float((x - y).abs().max()) for x, y in zip(p0, p1))
+    print("ragged last minibatch, captured + eager vs eager: max parameter distance %.3e, max loss difference %.3e"
+          % (worst, float((l0 - l1).abs().max())))
+    assert bool(torch.isfinite(l0).all())
+    assert torch.equal(l0, l1) and all(torch.equal(x, y) for x, y in zip(p0, p1))

@@ -10,13 +10,14 @@ import torch
 
 import ref_harness as rh
 
-pytestmark = pytest.mark.skipif(not rh.reference_available(), reason="reference tree not present")
+needs_reference = pytest.mark.skipif(not rh.reference_available(), reason="reference tree not present")
 
 
 class _Sp(object):
     shape = (8,)
 
 
+@needs_reference
 @pytest.mark.parametrize("clipped", [True, False])   # False: the reference's scalar-MSE branch (ppo.py:178-182)
 def test_losses_and_adam_step_match_reference_jointppo(clipped):
     rh.import_reference()
@@ -73,6 +74,7 @@ def test_losses_and_adam_step_match_reference_jointppo(clipped):
                .state_dict().items())  # sanity: weights did move / are not trivially equal
 
 
+@needs_reference
 def test_all_dead_minibatch_gives_zero_losses():
     from emergent_multiagent_strategies_amd.mpnn import MPNN
     from emergent_multiagent_strategies_amd.learner import ppo_losses
@@ -85,6 +87,7 @@ def test_all_dead_minibatch_gives_zero_losses():
     assert float(vl) == 0 and float(al) == 0 and float(ent) == 0 and torch.isfinite(vl)
 
 
+@needs_reference
 def test_reference_sampling_draws_the_reference_minibatches():
     """BatchedLearner(reference_sampling=True)'s index sets == the ones magent_feed_forward_generator (ppo.py:207-246) draws
     from the same torch seed: rollouts whose observation column 0 holds the flat sample index t * P + p make the reference's
@@ -108,3 +111,37 @@ def test_reference_sampling_draws_the_reference_minibatches():
     for ge, we in zip(got, want):
         for g, w in zip(ge, we):
             assert torch.equal(g, w)
+
+
+@pytest.mark.parametrize("mask_means", [(0.5, 0.0), (0.0, 0.0)])    # one rank's minibatch all dead; both (the guard: divide by 1)
+@pytest.mark.parametrize("layout", ["packed", "gflat"])
+def test_exchange_arithmetic_on_a_two_rank_flat_buffer(layout, mask_means):
+    """learner.finish_exchange_ -- the one place that turns the all-reduced [gradients | 3 loss sums | mask mean] buffer into
+    the union minibatch's gradients and losses -- on the sum of two hand-made ranks, for both layouts: the tail directly
+    behind the packed autograd gradients, and mpnn_pack.FlatPolicy.gflat's (tail at PF_FLOATS, spare floats behind it).
+    Expected: the same two float32 divisions (/ world, / all-rank mask mean or 1), element by element, bit for bit."""
+    from emergent_multiagent_strategies_amd import mpnn_pack
+    from emergent_multiagent_strategies_amd.learner import finish_exchange_
+    n, size = (37, 37 + 4) if layout == "packed" else (mpnn_pack.PF_FLOATS, mpnn_pack.PF_FLOATS + 8)
+    rs = np.random.RandomState(5)
+    ranks = []
+    for mm in mask_means:
+        r = np.zeros(size, np.float32)
+        r[:n] = rs.randn(n).astype(np.float32) * (mm != 0)      # an all-dead minibatch has no gradient and no loss
+        r[n:n + 3] = rs.rand(3).astype(np.float32) * (mm != 0)
+        r[n + 3] = mm
+        r[n + 4:] = 7.0                                          # spare floats: whatever they hold, the tail is found at n
+        ranks.append(r)
+    summed = ranks[0] + ranks[1]                                 # the all-reduce
+    mean = summed / np.float32(2)
+    mm = mean[n + 3]
+    want = mean / (mm if mm != 0 else np.float32(1))
+    flat = torch.from_numpy(summed.copy())
+    losses = finish_exchange_(flat, n, 2)
+    assert np.array_equal(flat.numpy()[:n + 4], want[:n + 4])
+    assert np.array_equal(losses.numpy(), want[n:n + 3]) and losses.data_ptr() == flat[n:].data_ptr()   # a view of flat
+    assert np.isfinite(flat.numpy()).all()
+    if mask_means == (0.0, 0.0):
+        assert not flat.numpy()[:n + 4].any()                    # 0 / 1, not 0 / 0
+    else:
+        assert flat[n + 3] == 1.0 and np.array_equal(flat.numpy()[:n], (ranks[0][:n] / np.float32(2)) / np.float32(0.25))

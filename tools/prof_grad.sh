@@ -14,7 +14,7 @@ for r in rows[:14]:
     print("%-84s calls %6s avg %9.1f us  total %8.2f ms  %5.1f%%" % (r["Name"][:84], r["Calls"], float(r["AverageNs"]) / 1e3, float(r["TotalDurationNs"]) / 1e6, float(r["Percentage"])))
 PY
 }
-for cfg in "3 3" "3 3 share" "5 5"; do
+for cfg in "3 3" "5 5"; do
   d=$out/g_$(echo $cfg | tr ' ' '_')
   rocprofv3 --kernel-trace --stats -f csv -d $d -o g -- python $root/tools/prof_grad.py $cfg > $d.log 2>&1
   tail -1 $d.log; show $d
