@@ -11,7 +11,9 @@ from .env import BatchedFortAttack, FortAttackGlobalEnv, make_fortattack_env  # 
 from .mpnn import MPNN  # noqa: F401
 from .learner import BatchedLearner  # noqa: F401
 from .rlagent import JointPPO, Neo  # noqa: F401
+from .crossplay import CrossPlay, crossplay_cells, crossplay_rows  # noqa: F401
 
 __all__ = ["BatchedFortAttack", "FortAttackGlobalEnv", "make_fortattack_env", "JointRolloutStorage",
-           "RolloutStorage", "FaError", "Box", "Discrete", "MASpace", "MPNN", "BatchedLearner", "Neo", "JointPPO"]
+           "RolloutStorage", "FaError", "Box", "Discrete", "MASpace", "MPNN", "BatchedLearner", "Neo", "JointPPO",
+           "CrossPlay", "crossplay_cells", "crossplay_rows"]
 from . import render  # noqa: F401

@@ -45,7 +45,8 @@ class PolicyIO(C.Structure):
     _fields_ = [("obs", c_p), ("weights", c_p * 2), ("value", c_p), ("action", c_p), ("log_prob", c_p),
                 ("counter", c_p), ("seed", C.c_uint64), ("step", C.c_int32), ("deterministic", C.c_int32),
                 ("value_only", C.c_int32), ("attacker_pool", c_p), ("pool_size", C.c_int32), ("env_strategy", c_p),
-                ("team_attn", c_p * 2), ("opp_attn", c_p * 2)]   # attention export: NULL (the zero default) = not wanted
+                ("team_attn", c_p * 2), ("opp_attn", c_p * 2),   # attention export: NULL (the zero default) = not wanted
+                ("guard_pool", c_p), ("guard_pool_size", C.c_int32), ("env_guard_strategy", c_p)]   # appended: offsets above stay
 
 
 class PPOGradIO(C.Structure):
@@ -104,6 +105,9 @@ EXPORTS = {
     "fa_after_update": (C.c_int, [c_p, c_p]),
     "fa_policy_act": (C.c_int, [c_p, C.POINTER(PolicyIO), c_p]),
     "fa_collect_act": (C.c_int, [c_p, C.c_int32, C.POINTER(PolicyIO), c_p]),
+    "fa_match_begin": (C.c_int, [c_p, c_p, C.c_int32, C.c_int32, c_p]),
+    "fa_match_latch": (C.c_int, [c_p, c_p]),
+    "fa_match_table": (C.c_int, [c_p, c_p, C.POINTER(C.c_int32), c_p]),
     "fa_policy_weight_floats": (C.c_int64, []),
     "fa_policy_plain_floats": (C.c_int64, []),
     "fa_attend_forward": (C.c_int, [c_p, c_p, c_p, c_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_p]),

@@ -10,6 +10,7 @@
 #include "fa_device.h"
 #include "experiments/fa_step_experiments.h"
 #include "fa_policy.h"
+#include "fa_match.h"
 #include "fa_train.h"
 #include "fortattack.h"
 
@@ -79,8 +80,10 @@ struct fa_env {
     int adv_blocks;
     int choice_k;        // fa_set_reset_choice
     int32_t *choice_out;
-    int32_t *grp_env_list, *grp_tile_strategy; // fused policy with an attacker ensemble: envs grouped by strategy
+    int32_t *grp_env_list[2], *grp_tile_strategy[2]; // fused policy with a guard [0] / attacker [1] ensemble: envs grouped by strategy
     int grp_tiles_max;
+    // match bookkeeping (fa_match.hip): baseline + latched counters per env, see fa_match_begin
+    FaMatch match;
 };
 
 namespace {
@@ -276,8 +279,18 @@ int fa_create(const fa_config *cfg, fa_env **out) {
     const int n_max = cfg->num_guards > cfg->num_attackers ? cfg->num_guards : cfg->num_attackers;
     const int tile_envs = fused_ok ? 64 / n_max : 1;
     env->grp_tiles_max = fused_ok ? (cfg->num_envs + tile_envs - 1) / tile_envs + FA_POLICY_MAX_POOL : 0;
-    const size_t o_gel = carve((size_t)env->grp_tiles_max * (FA_POLICY_ROWS / n_max + 1) * sizeof(int32_t));
-    const size_t o_gts = carve((size_t)env->grp_tiles_max * sizeof(int32_t));
+    size_t o_gel[2], o_gts[2];
+    for (int t = 0; t < 2; ++t) {
+        o_gel[t] = carve((size_t)env->grp_tiles_max * (FA_POLICY_ROWS / n_max + 1) * sizeof(int32_t));
+        o_gts[t] = carve((size_t)env->grp_tiles_max * sizeof(int32_t));
+    }
+    // match bookkeeping: baseline and latched copies of the three counters, the per-env cell / latch flag, two scalars
+    const bool match_ok = cfg->track_counters != 0;
+    const size_t o_mrc = carve(match_ok ? 2 * E * 3 * sizeof(uint32_t) : 0);
+    const size_t o_mae = carve(match_ok ? 2 * EN * sizeof(uint32_t) : 0);
+    const size_t o_mrw = carve(match_ok ? 2 * EN * sizeof(double) : 0);
+    const size_t o_mce = carve(match_ok ? 2 * E * sizeof(int32_t) : 0);
+    const size_t o_msc = carve(2 * sizeof(int32_t));
     env->slab_bytes = off;
     hipError_t he = hipMalloc(&env->slab, env->slab_bytes);
     if (he != hipSuccess) {
@@ -306,8 +319,23 @@ int fa_create(const fa_config *cfg, fa_env **out) {
     env->s.alive_end = reinterpret_cast<uint32_t *>(b + o_ale);
     env->adv_partial = reinterpret_cast<double *>(b + o_adv);
     env->adv_stats = reinterpret_cast<double *>(b + o_advs);
-    env->grp_env_list = reinterpret_cast<int32_t *>(b + o_gel);
-    env->grp_tile_strategy = reinterpret_cast<int32_t *>(b + o_gts);
+    for (int t = 0; t < 2; ++t) {
+        env->grp_env_list[t] = reinterpret_cast<int32_t *>(b + o_gel[t]);
+        env->grp_tile_strategy[t] = reinterpret_cast<int32_t *>(b + o_gts[t]);
+    }
+    if (match_ok) {
+        FaMatch &m = env->match;
+        m.base_rc = reinterpret_cast<uint32_t *>(b + o_mrc);
+        m.lat_rc = m.base_rc + E * 3;
+        m.base_alive = reinterpret_cast<uint32_t *>(b + o_mae);
+        m.lat_alive = m.base_alive + EN;
+        m.base_rew = reinterpret_cast<double *>(b + o_mrw);
+        m.lat_rew = m.base_rew + EN;
+        m.cell = reinterpret_cast<int32_t *>(b + o_mce);
+        m.latched = m.cell + E;
+        m.remaining = reinterpret_cast<int32_t *>(b + o_msc);
+        m.overrun = m.remaining + 1;
+    }
 
     // construction state (core.py:102-104): alive, prevDist None (NaN); positions are
     // defined by the first reset.
@@ -624,9 +652,10 @@ int fa_after_update(fa_env *env, void *stream) {
 
 static int policy_launch(fa_env *env, const float *obs, const float *wg, const float *wa, float *value, int64_t *action,
                          float *logp, const int64_t *counter, uint64_t seed, int step, int deterministic, int value_only,
-                         const float *pool, int pool_size, const int32_t *env_strategy, float *const *team_attn,
+                         const float *pool, int pool_size, const int32_t *env_strategy, const float *guard_pool,
+                         int guard_pool_size, const int32_t *env_guard_strategy, float *const *team_attn,
                          float *const *opp_attn, void *stream, const char *who) {
-    if (!obs || !wg || (!wa && pool_size <= 0))
+    if (!obs || (!wg && guard_pool_size <= 0) || (!wa && pool_size <= 0))
         return fail(FA_ERR_INVALID, std::string(who) + ": obs and both teams' weight buffers are required");
     if (!value_only && (!action || !logp)) return fail(FA_ERR_INVALID, std::string(who) + ": action and log_prob are required");
     if (value_only && !value) return fail(FA_ERR_INVALID, std::string(who) + ": value_only needs value");
@@ -634,6 +663,8 @@ static int policy_launch(fa_env *env, const float *obs, const float *wg, const f
         return fail(FA_ERR_INVALID, std::string(who) + ": teams of more than 8 agents are not supported by the fused policy");
     if (pool_size > 0 && (!pool || !env_strategy || pool_size > FA_POLICY_MAX_POOL))
         return fail(FA_ERR_INVALID, std::string(who) + ": an attacker pool needs weights, env_strategy and <= 64 strategies");
+    if (guard_pool_size > 0 && (!guard_pool || !env_guard_strategy || guard_pool_size > FA_POLICY_MAX_POOL))
+        return fail(FA_ERR_INVALID, std::string(who) + ": a guard pool needs guard_pool, env_guard_strategy and <= 64 strategies");
     DeviceGuard guard(env->cfg.device_id);
     hipStream_t s = static_cast<hipStream_t>(stream);
     FaPolicyArgs a;
@@ -657,12 +688,18 @@ static int policy_launch(fa_env *env, const float *obs, const float *wg, const f
         a.team_attn[t] = team_attn[t];
         a.opp_attn[t] = opp_attn[t];
     }
-    if (pool_size > 0) { // group the envs into tiles of equal strategy, then one launch over the grouped tiles
-        FA_HIP(fa_launch_group_envs(env_strategy, a.E, pool_size, a.G, a.A, env->grp_env_list, env->grp_tile_strategy,
+    if (pool_size > 0 || guard_pool_size > 0) { // group each pooled team's envs into tiles of equal strategy, then one launch
+        const int32_t *const strat[2] = {env_guard_strategy, env_strategy};
+        const float *const pools[2] = {guard_pool, pool};
+        const int sizes[2] = {guard_pool_size > 0 ? guard_pool_size : 0, pool_size > 0 ? pool_size : 0};
+        FA_HIP(fa_launch_group_envs(strat, a.E, sizes, a.G, a.A, env->grp_env_list, env->grp_tile_strategy,
                                     env->grp_tiles_max, s));
-        a.pool = pool;
-        a.env_list = env->grp_env_list;
-        a.tile_strategy = env->grp_tile_strategy;
+        for (int t = 0; t < 2; ++t) {
+            if (sizes[t] == 0) continue;
+            a.pool[t] = pools[t];
+            a.env_list[t] = env->grp_env_list[t];
+            a.tile_strategy[t] = env->grp_tile_strategy[t];
+        }
         a.tiles = env->grp_tiles_max;
     }
     FA_HIP(fa_launch_policy(a, s));
@@ -673,7 +710,8 @@ int fa_policy_act(fa_env *env, const fa_policy_io *io, void *stream) {
     if (!env || !io) return fail(FA_ERR_INVALID, "fa_policy_act: null argument");
     return policy_launch(env, io->obs, io->weights[0], io->weights[1], io->value, io->action, io->log_prob, io->counter,
                          io->seed, io->step, io->deterministic, io->value_only, io->attacker_pool, io->pool_size,
-                         io->env_strategy, io->team_attn, io->opp_attn, stream, "fa_policy_act");
+                         io->env_strategy, io->guard_pool, io->guard_pool_size, io->env_guard_strategy, io->team_attn,
+                         io->opp_attn, stream, "fa_policy_act");
 }
 
 int fa_collect_act(fa_env *env, int32_t step, const fa_policy_io *io, void *stream) {
@@ -688,8 +726,47 @@ int fa_collect_act(fa_env *env, int32_t step, const fa_policy_io *io, void *stre
     return policy_launch(env, st.obs + (size_t)step * EN * FA_OBS_DIM, io->weights[0], io->weights[1],
                          st.value_preds + (size_t)step * EN, value_only ? nullptr : st.actions + (size_t)step * EN,
                          value_only ? nullptr : st.action_log_probs + (size_t)step * EN, io->counter, io->seed, step,
-                         io->deterministic, value_only, io->attacker_pool, io->pool_size, io->env_strategy, io->team_attn,
-                         io->opp_attn, stream, "fa_collect_act");
+                         io->deterministic, value_only, io->attacker_pool, io->pool_size, io->env_strategy, io->guard_pool,
+                         io->guard_pool_size, io->env_guard_strategy, io->team_attn, io->opp_attn, stream, "fa_collect_act");
+}
+
+// ---- match bookkeeping (fa_match.hip) ------------------------------------------------------------------
+int fa_match_begin(fa_env *env, const int32_t *env_cell, int32_t n_cells, int32_t episodes_per_env, void *stream) {
+    if (!env || !env_cell) return fail(FA_ERR_INVALID, "fa_match_begin: null argument");
+    if (!env->cfg.track_counters) return fail(FA_ERR_STATE, "fa_match_begin: the handle was created with track_counters = 0");
+    if (n_cells < 1 || episodes_per_env < 1) return fail(FA_ERR_INVALID, "fa_match_begin: need n_cells >= 1 and episodes_per_env >= 1");
+    DeviceGuard guard(env->cfg.device_id);
+    env->match.n_cells = n_cells;
+    env->match.episodes_per_env = episodes_per_env;
+    env->match.begun = 1;
+    FA_HIP(fa_launch_match_begin(env->s, env->match, env_cell, env->cfg.num_envs, env->N, static_cast<hipStream_t>(stream)));
+    return FA_OK;
+}
+
+int fa_match_latch(fa_env *env, void *stream) {
+    if (!env) return fail(FA_ERR_INVALID, "fa_match_latch: null env");
+    if (!env->cfg.track_counters) return fail(FA_ERR_STATE, "fa_match_latch: the handle was created with track_counters = 0");
+    if (!env->match.begun) return fail(FA_ERR_STATE, "fa_match_latch: no match begun (fa_match_begin)");
+    DeviceGuard guard(env->cfg.device_id);
+    FA_HIP(fa_launch_match_latch(env->s, env->match, env->cfg.num_envs, env->N, static_cast<hipStream_t>(stream)));
+    return FA_OK;
+}
+
+int fa_match_table(fa_env *env, double *raw, int32_t *remaining_out, void *stream) {
+    if (!env || !raw) return fail(FA_ERR_INVALID, "fa_match_table: null argument");
+    if (!env->cfg.track_counters) return fail(FA_ERR_STATE, "fa_match_table: the handle was created with track_counters = 0");
+    if (!env->match.begun) return fail(FA_ERR_STATE, "fa_match_table: no match begun (fa_match_begin)");
+    DeviceGuard guard(env->cfg.device_id);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    FA_HIP(fa_launch_match_table(env->s, env->match, env->cfg.num_envs, env->N, raw, s));
+    int32_t flags[2] = {0, 0}; // remaining, overrun: adjacent device scalars
+    FA_HIP(hipMemcpyAsync(flags, env->match.remaining, sizeof(flags), hipMemcpyDeviceToHost, s));
+    FA_HIP(hipStreamSynchronize(s));
+    if (remaining_out) *remaining_out = flags[0];
+    if (flags[1])
+        return fail(FA_ERR_STATE, "fa_match_table: an env played beyond episodes_per_env before it was latched "
+                                  "(fa_match_latch must follow every one-step launch)");
+    return FA_OK;
 }
 
 int64_t fa_policy_weight_floats(void) { return FA_POLICY_WEIGHT_FLOATS; }

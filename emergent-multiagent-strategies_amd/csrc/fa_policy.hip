@@ -129,15 +129,16 @@ __global__ __launch_bounds__(NW * 64, NRB == 2 ? 2 : 1) void fa_policy_kernel(Fa
     const unsigned inv_n = 65536u / (unsigned)n + 1u, inv_m = 65536u / (unsigned)m + 1u;
     auto div_n = [&](int r) { return (int)(((unsigned)r * inv_n) >> 16); };
     auto div_m = [&](int r) { return (int)(((unsigned)r * inv_m) >> 16); };
-    // which envs: a contiguous range, or -- ensemble of attacker strategies -- the tile's slots of the
-    // strategy-sorted env list (every env of a tile then shares one set of attacker weights)
+    // which envs: a contiguous range, or -- this team runs an ensemble of strategies -- the tile's slots of the team's
+    // strategy-sorted env list (every env of a tile then shares one set of the team's weights)
     __shared__ int sE[PR];
     const float *W = a.w[team];
-    if (a.env_list) {
-        const int strat = a.tile_strategy[blockIdx.x];
+    const int32_t *const elist = a.env_list[team];
+    if (elist) {
+        const int strat = a.tile_strategy[team][blockIdx.x];
         if (strat < 0) return;
-        if (team == 1) W = a.pool + (size_t)strat * FA_POLICY_WEIGHT_FLOATS;
-        if (tid < ET) sE[tid] = a.env_list[blockIdx.x * ET + tid];
+        W = a.pool[team] + (size_t)strat * FA_POLICY_WEIGHT_FLOATS;
+        if (tid < ET) sE[tid] = elist[blockIdx.x * ET + tid];
     } else {
         const int e0 = blockIdx.x * ET;
         if (e0 >= a.E) return;
@@ -441,11 +442,19 @@ _Pragma("unroll")
     FA_PL_TICK(31)
 }
 #undef FA_POLICY_SPLIT
-// Ensemble: sort the envs into tiles of equal strategy.  One workgroup: histogram, tile ranges per
-// strategy, scatter (the order inside a strategy's tiles is arbitrary -- every output is per env and the
-// sampling key holds the env index, so results do not depend on it).
-__global__ __launch_bounds__(1024) void fa_group_envs_kernel(const int32_t *__restrict__ strat, int E, int K, int ET, int tiles_max,
-                                                            int32_t *__restrict__ env_list, int32_t *__restrict__ tile_strategy) {
+// Ensemble: sort the envs into tiles of equal strategy.  One workgroup per team (blockIdx.x; a team without a pool returns):
+// histogram, tile ranges per strategy, scatter (the order inside a strategy's tiles is arbitrary -- every output is per env and
+// the sampling key holds the env index, so results do not depend on it).
+struct FaGroupArgs {
+    const int32_t *strat[2];
+    int32_t *env_list[2], *tile_strategy[2];
+    int32_t K[2];
+};
+__global__ __launch_bounds__(1024) void fa_group_envs_kernel(FaGroupArgs g, int E, int ET, int tiles_max) {
+    const int32_t *__restrict__ strat = g.strat[blockIdx.x];
+    if (!strat) return;
+    int32_t *__restrict__ env_list = g.env_list[blockIdx.x], *__restrict__ tile_strategy = g.tile_strategy[blockIdx.x];
+    const int K = g.K[blockIdx.x];
     __shared__ int cnt[FA_POLICY_MAX_POOL], start[FA_POLICY_MAX_POOL], cur[FA_POLICY_MAX_POOL];
     const int tid = threadIdx.x;
     if (tid < FA_POLICY_MAX_POOL) { cnt[tid] = 0; cur[tid] = 0; }
@@ -483,16 +492,22 @@ static int policy_rows(int E, int G, int A) {
 }
 int fa_policy_tile_envs(int E, int G, int A) { return policy_rows(E, G, A) / (G > A ? G : A); }
 
-hipError_t fa_launch_group_envs(const int32_t *env_strategy, int E, int pool_size, int G, int A, int32_t *env_list,
-                                int32_t *tile_strategy, int tiles_max, hipStream_t st) {
-    hipLaunchKernelGGL(fa_group_envs_kernel, dim3(1), dim3(1024), 0, st, env_strategy, E, pool_size, fa_policy_tile_envs(E, G, A),
-                       tiles_max, env_list, tile_strategy);
+hipError_t fa_launch_group_envs(const int32_t *const env_strategy[2], int E, const int pool_size[2], int G, int A,
+                                int32_t *const env_list[2], int32_t *const tile_strategy[2], int tiles_max, hipStream_t st) {
+    FaGroupArgs g;
+    for (int t = 0; t < 2; ++t) {
+        g.strat[t] = pool_size[t] > 0 ? env_strategy[t] : nullptr;
+        g.env_list[t] = env_list[t];
+        g.tile_strategy[t] = tile_strategy[t];
+        g.K[t] = pool_size[t];
+    }
+    hipLaunchKernelGGL(fa_group_envs_kernel, dim3(2), dim3(1024), 0, st, g, E, fa_policy_tile_envs(E, G, A), tiles_max);
     return hipGetLastError();
 }
 
 hipError_t fa_launch_policy(const FaPolicyArgs &a, hipStream_t st) {
     const int ET = fa_policy_tile_envs(a.E, a.G, a.A);
-    const int tiles = a.env_list ? a.tiles : (a.E + ET - 1) / ET;
+    const int tiles = (a.env_list[0] || a.env_list[1]) ? a.tiles : (a.E + ET - 1) / ET;
     // the exporting instantiation iff any of the four attention matrices is wanted (a null one among them is skipped)
     const bool attn = a.team_attn[0] || a.team_attn[1] || a.opp_attn[0] || a.opp_attn[1];
     const bool rows64 = policy_rows(a.E, a.G, a.A) == 64;

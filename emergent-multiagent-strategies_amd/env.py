@@ -257,18 +257,26 @@ class BatchedFortAttack(object):
         _lib.check(self._lib.fa_after_update(self._h, _stream()), "fa_after_update")
 
     # -- fused policy (csrc/fa_policy.hip) ----------------------------------------------------
-    def _policy_io(self, w_guards, w_attackers, seed, counter, step, deterministic, value_only, pool, env_strategy):
+    def _policy_io(self, w_guards, w_attackers, seed, counter, step, deterministic, value_only, pool, env_strategy,
+                   guard_pool=None, env_guard_strategy=None):
         nfl = self._lib.fa_policy_weight_floats()
         io = _lib.PolicyIO()
         for w in (w_guards, w_attackers):
             assert w is None or (w.is_cuda and w.dtype == torch.float32 and w.is_contiguous() and w.numel() == nfl)
-        io.weights[0], io.weights[1] = w_guards.data_ptr(), (w_attackers.data_ptr() if w_attackers is not None else None)
+        io.weights[0] = w_guards.data_ptr() if w_guards is not None else None
+        io.weights[1] = w_attackers.data_ptr() if w_attackers is not None else None
         io.counter = _ptr(counter)
         io.seed, io.step, io.deterministic, io.value_only = int(seed), int(step), int(bool(deterministic)), int(bool(value_only))
         if pool is not None:   # (K, weight_floats) packed attacker strategies + per-env strategy index
             assert pool.is_cuda and pool.dtype == torch.float32 and pool.is_contiguous() and pool.shape[1] == nfl
             assert env_strategy.dtype == torch.int32 and env_strategy.is_contiguous() and env_strategy.numel() == self.E
             io.attacker_pool, io.pool_size, io.env_strategy = _ptr(pool), int(pool.shape[0]), _ptr(env_strategy)
+        if guard_pool is not None:   # the same for the guards: (Kg, weight_floats) + per-env guard strategy index
+            assert guard_pool.is_cuda and guard_pool.dtype == torch.float32 and guard_pool.is_contiguous() and guard_pool.shape[1] == nfl
+            assert (env_guard_strategy.is_cuda and env_guard_strategy.dtype == torch.int32 and env_guard_strategy.is_contiguous()
+                    and env_guard_strategy.numel() == self.E)
+            io.guard_pool, io.guard_pool_size = _ptr(guard_pool), int(guard_pool.shape[0])
+            io.env_guard_strategy = _ptr(env_guard_strategy)
         return io
 
     def attn_shapes(self):
@@ -290,10 +298,12 @@ class BatchedFortAttack(object):
             io.team_attn[t], io.opp_attn[t] = _ptr(pair[0]), _ptr(pair[1])
 
     def policy_act(self, obs, w_guards, w_attackers, seed=0, counter=None, step=0, deterministic=False,
-                   value_only=False, out=None, pool=None, env_strategy=None, return_attn=False, attn_out=None):
+                   value_only=False, out=None, pool=None, env_strategy=None, return_attn=False, attn_out=None,
+                   guard_pool=None, env_guard_strategy=None):
         """fa_policy_act: both teams' MPNN forward + sampling on an observation row obs (E, N, 6) float32.
         w_*: packed weight buffers (mpnn_pack.pack_policy); with `pool` (K, floats) + `env_strategy` (E) int32
-        env e's attackers run strategy env_strategy[e] of the pool.  Returns (value, action, log_prob), each
+        env e's attackers run strategy env_strategy[e] of the pool; `guard_pool` + `env_guard_strategy` do the same for the
+        guards (w_guards may then be None).  Returns (value, action, log_prob), each
         (E, N) (action / log_prob are None with value_only).  return_attn: a fourth value ((team_g, opp_g), (team_a, opp_a)),
         the attention maps of this forward (policy.attn_mat / opp_attn_mat of the reference, mpnn.py:139-140, :158-166):
         float32 (E, n, n) -- the last message-passing round's, zero diagonal -- and (E, n, m) per team, written into
@@ -304,7 +314,8 @@ class BatchedFortAttack(object):
             self._new((self.E, self.N), torch.float32),
             None if value_only else self._new((self.E, self.N), torch.int64),
             None if value_only else self._new((self.E, self.N), torch.float32))
-        io = self._policy_io(w_guards, w_attackers, seed, counter, step, deterministic, value_only, pool, env_strategy)
+        io = self._policy_io(w_guards, w_attackers, seed, counter, step, deterministic, value_only, pool, env_strategy,
+                             guard_pool, env_guard_strategy)
         io.obs, io.value, io.action, io.log_prob = _ptr(obs), _ptr(value), _ptr(action), _ptr(logp)
         if return_attn or attn_out is not None:
             attn_out = self.new_attn_out() if attn_out is None else attn_out
@@ -315,14 +326,40 @@ class BatchedFortAttack(object):
         return value, action, logp
 
     def collect_act(self, step, w_guards, w_attackers, seed=0, counter=None, deterministic=False, value_only=False,
-                    pool=None, env_strategy=None, attn_out=None):
+                    pool=None, env_strategy=None, attn_out=None, guard_pool=None, env_guard_strategy=None):
         """fa_collect_act: the policies act on storage.obs[step] and write value_preds / actions /
         action_log_probs[step] (value_only: only value_preds[step], the V(obs[T]) of wrap_horizon).  attn_out =
         ((team_g, opp_g), (team_a, opp_a)): the forward's attention maps go there too (see policy_act)."""
-        io = self._policy_io(w_guards, w_attackers, seed, counter, step, deterministic, value_only, pool, env_strategy)
+        io = self._policy_io(w_guards, w_attackers, seed, counter, step, deterministic, value_only, pool, env_strategy,
+                             guard_pool, env_guard_strategy)
         if attn_out is not None:
             self._set_attn(io, attn_out)
         _lib.check(self._lib.fa_collect_act(self._h, int(step), C.byref(io), _stream()), "fa_collect_act")
+
+    # -- match bookkeeping (csrc/fa_match.hip) ---------------------------------------------------
+    def match_begin(self, env_cell, n_cells, episodes_per_env):
+        """fa_match_begin: env_cell (E) int32 device tensor, the match-up cell of every env.  The counters of now become the
+        baseline; from here every env contributes exactly `episodes_per_env` episodes to its cell."""
+        assert env_cell.is_cuda and env_cell.dtype == torch.int32 and env_cell.is_contiguous() and env_cell.numel() == self.E
+        _lib.check(self._lib.fa_match_begin(self._h, _ptr(env_cell), int(n_cells), int(episodes_per_env), _stream()),
+                   "fa_match_begin")
+        self._match_cells = int(n_cells)
+
+    def match_latch(self):
+        """fa_match_latch: after every one-step launch; latches the envs that have just finished their quota."""
+        _lib.check(self._lib.fa_match_latch(self._h, _stream()), "fa_match_latch")
+
+    def match_table(self, out=None):
+        """fa_match_table -> (raw, remaining): raw (n_cells, 5 + 2N) float64 on the device, per cell [latched envs, episodes,
+        result_count[3], alive_at_end[N], episode_reward_sum[N]] summed over its latched envs; remaining = envs not latched
+        yet.  Synchronises the stream.  Raises FaError if an env overran its quota (a latch was skipped)."""
+        n_cells = getattr(self, "_match_cells", 0)
+        if out is None:
+            out = torch.zeros((max(n_cells, 1), 5 + 2 * self.N), dtype=torch.float64, device=self.device)
+        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= n_cells * (5 + 2 * self.N)
+        rem = C.c_int32(-1)
+        _lib.check(self._lib.fa_match_table(self._h, _ptr(out), C.byref(rem), _stream()), "fa_match_table")
+        return out, int(rem.value)
 
     # -- state snapshot ----------------------------------------------------------------
     _F64 = ("pos_x", "pos_y", "vel_x", "vel_y", "ang", "prev_dist")

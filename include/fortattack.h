@@ -304,6 +304,16 @@ typedef struct fa_policy_io {
      * honours them as fa_policy_act does. */
     float *team_attn[2];
     float *opp_attn[2];
+    /* Ensemble of frozen GUARD strategies, the mirror of attacker_pool / pool_size / env_strategy (appended here so that the
+     * offsets above stay put): with guard_pool_size > 0 env e's guards run strategy env_guard_strategy[e] of guard_pool
+     * instead of weights[0], which may then be NULL.  The reference's result scripts load a series of guard checkpoints
+     * and play each against every attacker strategy (test_fortattack_v2.py:56-124,
+     * test_fortattack_v2_gen_plot_data.py:61-141); with both pools one launch plays the whole matrix.  Each team's tiles are
+     * sorted by that team's own strategy -- one partly filled tile per strategy, not per (guard, attacker) cell.  With a
+     * guard pool, env e's guard rows of team_attn[0] / opp_attn[0] are those of the strategy it ran. */
+    const float *guard_pool;           /* device: guard_pool_size packed buffers back to back, or NULL */
+    int32_t guard_pool_size;           /* 0 = no guard ensemble; at most 64 */
+    const int32_t *env_guard_strategy; /* device (E): 0..guard_pool_size-1 */
 } fa_policy_io;
 int fa_policy_act(fa_env *env, const fa_policy_io *io, void *stream);
 /* The same on the bound storage (io->obs / value / action / log_prob are ignored): reads obs[step], writes
@@ -311,6 +321,30 @@ int fa_policy_act(fa_env *env, const fa_policy_io *io, void *stream);
  * RolloutStorage.insert, learner.py:143-172, storage.py:33-43); with value_only only value_preds[step]
  * (wrap_horizon's V(obs[T]), learner.py:196-202). */
 int fa_collect_act(fa_env *env, int32_t step, const fa_policy_io *io, void *stream);
+/* ---- cross-play: a fixed number of episodes per match-up, tabled on the device ------------------------
+ * The reference's evaluation plays `num_eval_episodes` episodes per (guard checkpoint, attacker strategy) match-up and
+ * emits one row per match-up (test_fortattack_v2.py:56-124, rows :95-101; test_fortattack_v2_gen_plot_data.py:61-141).
+ * The handle's counters (fa_state_host: result_count / alive_at_end / episode_reward_sum) count whatever finished; summed
+ * over a window of steps they over-weight match-ups whose episodes are short.  These three calls make every env contribute
+ * exactly `episodes_per_env` episodes.  They need a handle created with track_counters != 0 (FA_ERR_STATE otherwise).
+ *
+ * fa_match_begin: env_cell is device (E) int32, the match-up cell 0..n_cells-1 of every env (an env with a cell outside
+ *   that range is played but tabled nowhere).  Records the counters as the baseline, clears the per-env latch and the
+ *   running return of any episode in flight, sets remaining = E.  Reset every env right after.
+ * fa_match_latch: call after EVERY one-step launch (fa_step / fa_collect_step with one step).  An env whose finished
+ *   episodes since the baseline have reached episodes_per_env is latched: its counters minus the baseline are copied
+ *   once and never change again (it keeps playing), and `remaining` drops by one.  At most one episode ends per env and
+ *   step, so a latched env holds exactly episodes_per_env episodes; an env found beyond its quota (latches were skipped)
+ *   raises a flag that makes fa_match_table fail.
+ * fa_match_table: raw is device (n_cells, 5 + 2N) float64; per cell, summed over its latched envs:
+ *   [latched envs, episodes, result_count[3] (attackers all dead, timeout, fort reached), alive_at_end[N],
+ *   episode_reward_sum[N]].  Raw sums: shards or ranks merge by plain addition.  The sums are taken in a fixed order
+ *   (no floating-point atomics): equal inputs give equal bits.  Synchronises the stream; *remaining_out (host, may be
+ *   NULL) receives the number of envs not yet latched.  FA_ERR_STATE if an env overran its quota. */
+int fa_match_begin(fa_env *env, const int32_t *env_cell, int32_t n_cells, int32_t episodes_per_env, void *stream);
+int fa_match_latch(fa_env *env, void *stream);
+int fa_match_table(fa_env *env, double *raw, int32_t *remaining_out, void *stream);
+
 /* number of floats of one team's packed weight buffer; of its leading float32 sections (= a plain-layout buffer) */
 int64_t fa_policy_weight_floats(void);
 int64_t fa_policy_plain_floats(void);
