@@ -170,26 +170,45 @@ __global__ __launch_bounds__(256) void fa_gae_coop_kernel(const float *__restric
 
 
 // ---- the collector tail in two launches: GAE + advantage moments, fold + normalisation --------------
-// fa_gae_mom_kernel = the cooperative scan whose scanning wave also leaves the workgroup's one-pass
-// advantage moments (ppo.py:121-123): S = sum(A - P), Q = sum((A - P)^2) per agent in fp64, with
-// A = returns[t] - value_preds[t] taken in float32 from the value the scan is about to store -- the
-// returns / value_preds re-read of fa_adv_onepass_vec_kernel and its launch disappear.  The entries at
-// the episode ends are left stale by the scan (storage.py:59-66 never visits them) but belong to the
-// statistics: their OLD returns (and value_preds) are gathered sparsely by the scanning wave behind the
-// chunk's scan, FA_GAEC_GATHER per lane and trip -- the wave is ahead of the loaders, the round trip hides
-// behind the next barrier.  (A dense prefetch of the old returns costs the 12.6 MB it reads: 21 us against
-// 15.4 for the plain scan; round 4's first attempt, a fifth wave + the sums inside the scan loop, 29 us;
-// the done flags requested by the scanning wave itself instead of a loader: 19.5 us -- a wave that stores
-// should not also wait for loads, the counter is one.)  The workgroup barrier is a raw s_barrier behind an
-// LDS wait, not __syncthreads(): the scanning wave's stores and gathers stay in flight across it.  Rows are
-// addressed through buffer descriptors (scalar row offset + the lane's 32-bit byte offset).
+// fa_gae_mom_kernel = a cooperative scan that also leaves the workgroup's one-pass advantage moments
+// (ppo.py:121-123): S = sum(A - P), Q = sum((A - P)^2) per agent in fp64, with A = returns[t] - value_preds[t]
+// taken in float32 from the value about to be stored -- the returns / value_preds re-read of
+// fa_adv_onepass_vec_kernel and its launch disappear.  The entries at the episode ends are left stale by the
+// scan (storage.py:59-66 never visits them) but belong to the statistics: their OLD returns (and value_preds)
+// are gathered sparsely, FA_GAEC_GATHER per lane and chunk.
+//
+// Eight waves share 64 columns, split by ROLE so that the one serial chain of the kernel -- g = delta + c * gae,
+// then the reset -- has a wave to itself (round 7; before, one wave carried the whole per-step work, 32 instructions
+// a step with three exec-mask changes, and the kernel ran at that wave's pace: 20 us against 10 for its loads,
+// barriers and stores):
+//   waves 1..3  loaders, partitioned by TIME: each fetches rewards / value_preds / masks / done flags for its share
+//               of the chunk's steps (plus the one row of overlap for v[t+1], m[t+1]), computes everything that does not
+//               depend on the previous step -- delta_t = r + g32 * v_next * m_next - v, c_t = gt32 * m_next, the step's
+//               flag (FA_GAES_*); the float32 expressions of fa_gae_kernel in the same order -- and leaves delta, c, the
+//               flag and v in LDS.  One chunk in flight per loader, all workgroups walk the step axis together
+//               (gae_scan_deep_prefetch.md).
+//   wave 0      the scan: reads delta, c, flag of a chunk from LDS in one batch; per step a multiply, an add, a
+//               select and the LDS write of g (over delta).  No global memory, no fp64.
+//   waves 4, 5  the stores, one chunk behind the scan, even / odd steps: ret = g + v to returns for valid lanes and live
+//               steps.  (A wave that stores should not also wait for bulk loads -- collector_tail_fusion.md -- so the
+//               stores stay off the loaders.)
+//   waves 6, 7  the fp64 moments, one chunk behind the scan, in the accumulation order the one-wave form had: wave 6 is its
+//               accumulator pair 0 (even k, descending t; a chunk's first FA_GAEC_GATHER stale entries requested behind the
+//               chunk and added at the top of the next, the rare remainder on the spot), wave 7 its pair 1 (odd k); the
+//               per-agent fold adds pair 0 + pair 1 per lane as before.  (All of this on ONE post wave: 29.4 us -- the work
+//               of a step is independent of the other steps, but at 8-9 cycles per instruction of such code a single wave
+//               needs 150 ns for it.)
+// A chunk passes through three trips: loaded in trip c, scanned in trip c + 1, posted in trip c + 2; every role runs
+// fa_gaes_trips(nc) trips with one barrier each.  The workgroup barrier is a raw s_barrier behind an LDS wait, not
+// __syncthreads(): loads, stores and gathers stay in flight across it.  Rows are addressed through buffer descriptors
+// (scalar row offset + the lane's 32-bit byte offset).
 // Pivot P_i: agent i's first GAE term of env 0, from the inputs alone, so that every workgroup and the
 // fold agree on it without a grid-wide exchange (any sample-sized value does: it only keeps S*S/n from
 // cancelling against Q).
 #define FA_GAEC_GATHER 4
-// the workgroup barrier between chunks: LDS traffic complete, then s_barrier.  NOT __syncthreads(): its fence also
-// waits for every global load and store in flight (vmcnt(0)) -- the loaders' next chunks and the scanning wave's
-// stores -- which is what pinned the first form of this kernel to one chunk in flight and a store drain per chunk.
+// the workgroup barrier between trips: LDS traffic complete, then s_barrier.  NOT __syncthreads(): its fence also
+// waits for every global load and store in flight (vmcnt(0)) -- the loaders' next chunks, the store waves'
+// stores, the gathers -- which is what pinned the first form of this kernel to one chunk in flight and a store drain per chunk.
 #define FA_GAEC_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 __device__ __forceinline__ float fa_gae_pivot(const float *__restrict__ rewards, const float *__restrict__ value_preds,
                                               const float *__restrict__ masks, int T, long long EN, int i, float g32) {
@@ -199,14 +218,51 @@ __device__ __forceinline__ float fa_gae_pivot(const float *__restrict__ rewards,
     return (delta + vp) - vp;
 }
 
-__global__ __launch_bounds__(256, 2) void fa_gae_mom_kernel(const float *__restrict__ rewards,
-                                                             const float *__restrict__ value_preds,
-                                                             const float *__restrict__ masks, float *__restrict__ returns,
-                                                             const uint8_t *__restrict__ done, int T, int E, int N, float g32,
-                                                             float gt32, double *__restrict__ partial) {
-    __shared__ float s_x[3][2][FA_GAEC_CHUNK][64]; // [rewards, value_preds, masks][chunk parity][step][column]
-    __shared__ uint8_t s_d[2][FA_GAEC_CHUNK][64];
-    __shared__ double s_sq[2][64];
+// The roles' shared arithmetic.  Loader l owns the steps k in [fa_gaes_first(l), fa_gaes_first(l + 1)) of every chunk.
+#define FA_GAES_LOADERS 3
+#define FA_GAES_THREADS (64 * (FA_GAES_LOADERS + 5)) // the scan, the loaders, two store waves, two moment waves
+// a step's flag byte in LDS
+#define FA_GAES_LIVE 0   // returns[t] is computed and stored, the advantage enters the moments
+#define FA_GAES_STALE 1  // t > 0 && done[t-1]: the accumulator restarts, returns[t] keeps its old value, which enters the moments
+#define FA_GAES_BELOW 2  // t < 0 (behind the last chunk's real steps): nothing
+constexpr int fa_gaes_first(int l) { return (l * FA_GAEC_CHUNK + FA_GAES_LOADERS - 1) / FA_GAES_LOADERS; }
+constexpr bool fa_gaes_one_owner_per_step() {
+    for (int k = 0; k < FA_GAEC_CHUNK; ++k) {
+        int owners = 0;
+        for (int l = 0; l < FA_GAES_LOADERS; ++l) owners += (k >= fa_gaes_first(l) && k < fa_gaes_first(l + 1)) ? 1 : 0;
+        if (owners != 1) return false;
+    }
+    return true;
+}
+// requests a loader has in flight: n rewards + n done flags + (n + 1) value_preds + (n + 1) masks
+constexpr int fa_gaes_max_requests() {
+    int most = 0;
+    for (int l = 0; l < FA_GAES_LOADERS; ++l) {
+        const int n = fa_gaes_first(l + 1) - fa_gaes_first(l);
+        most = 4 * n + 2 > most ? 4 * n + 2 : most;
+    }
+    return most;
+}
+static_assert(fa_gaes_one_owner_per_step(), "every step of a chunk has exactly one loader");
+static_assert(fa_gaes_max_requests() <= 63, "a wave has at most 63 vector-memory requests in flight (vmcnt)");
+// trip j: chunk j is loaded, chunk j - 1 scanned, chunk j - 2 posted (-1: the role idles, but still meets the barrier)
+__device__ __forceinline__ int fa_gaes_trips(int nc) { return nc + 2; }
+__device__ __forceinline__ int fa_gaes_load_chunk(int j, int nc) { return j < nc ? j : -1; }
+__device__ __forceinline__ int fa_gaes_scan_chunk(int j, int nc) { return (j >= 1 && j - 1 < nc) ? j - 1 : -1; }
+__device__ __forceinline__ int fa_gaes_post_chunk(int j, int nc) { return (j >= 2 && j - 2 < nc) ? j - 2 : -1; }
+template <int L> struct FaGaesLoader { static constexpr int first = fa_gaes_first(L), n = fa_gaes_first(L + 1) - fa_gaes_first(L); };
+template <int P> struct FaGaesParity { static constexpr int value = P; };
+
+__global__ __launch_bounds__(FA_GAES_THREADS) void fa_gae_mom_kernel(const float *__restrict__ rewards,
+                                                                     const float *__restrict__ value_preds,
+                                                                     const float *__restrict__ masks, float *__restrict__ returns,
+                                                                     const uint8_t *__restrict__ done, int T, int E, int N, float g32,
+                                                                     float gt32, double *__restrict__ partial) {
+    // [stage][step][column], 4-byte elements (and a byte per flag).  A chunk's delta is overwritten by its g in place; c
+    // lives from the load to the scan only: two stages.  70 KB + the fold's 2 KB: two workgroups per CU.
+    __shared__ float s_g[3][FA_GAEC_CHUNK][64], s_v[3][FA_GAEC_CHUNK][64], s_c[2][FA_GAEC_CHUNK][64];
+    __shared__ uint8_t s_f[3][FA_GAEC_CHUNK][64];
+    __shared__ double s_sq[2][2][64];  // [accumulator pair][S, Q][column]
     const long long EN = (long long)E * N;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); // wave: in a scalar register
     const long long colv = (long long)blockIdx.x * 64 + lane;
@@ -214,151 +270,190 @@ __global__ __launch_bounds__(256, 2) void fa_gae_mom_kernel(const float *__restr
     const long long col = valid ? colv : EN - 1; // idle lanes shadow the last column, store nothing
     const int e = (int)(col / N);
     const int nc = (T + FA_GAEC_CHUNK - 1) / FA_GAEC_CHUNK;
+    const int trips = fa_gaes_trips(nc);
     // chunk c holds steps t = T-1 - c*CHUNK - k, k = 0..CHUNK-1 (clamped loads below t = 0)
     // Rows are addressed through buffer descriptors: a wave-uniform row offset in a scalar register + the lane's
     // 32-bit byte offset.  (As 64-bit vector addresses the loads a loader keeps in flight cost it two registers each.)
     // Offsets fit 32 bits: (T + 1) * EN * 4 < 2^31 on this path.
     const unsigned rowb = (unsigned)EN * 4u;                                    // bytes per step of a (T, E, N) tensor
     const unsigned coff = (unsigned)col * 4u;
-    const float *src = wave == 1 ? rewards : (wave == 2 ? value_preds : masks);
-    const __amdgpu_buffer_rsrc_t rs_src =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(src), 0, (int)((unsigned)(T + 1) * rowb), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_ret = __builtin_amdgcn_make_buffer_rsrc(returns, 0, (int)((unsigned)(T + 1) * rowb), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_val =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(value_preds), 0, (int)((unsigned)(T + 1) * rowb), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_done =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(done), 0, (int)((unsigned)T * (unsigned)E), 0x00020000);
+    auto rsrc = [&](const void *p, unsigned bytes) {
+        return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
+    };
+    const __amdgpu_buffer_rsrc_t rs_rew = rsrc(rewards, (unsigned)T * rowb);
+    const __amdgpu_buffer_rsrc_t rs_val = rsrc(value_preds, (unsigned)(T + 1) * rowb);
+    const __amdgpu_buffer_rsrc_t rs_msk = rsrc(masks, (unsigned)(T + 1) * rowb);
+    const __amdgpu_buffer_rsrc_t rs_ret = rsrc(returns, (unsigned)(T + 1) * rowb);
+    const __amdgpu_buffer_rsrc_t rs_done = rsrc(done, (unsigned)T * (unsigned)E);
     auto ldf = [&](const __amdgpu_buffer_rsrc_t &rs, unsigned voff, unsigned soff) -> float {
         // (readfirstlane: the row offset IS uniform, but computed with a vector clamp it gets a waterfall loop per load)
         return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)voff, __builtin_amdgcn_readfirstlane((int)soff), 0));
     };
-    // a loader's chunk: 32 floats of its tensor; wave 3 also the 32 done flags of the lane's env
-    struct Chunk { float x[FA_GAEC_CHUNK]; uint8_t d[FA_GAEC_CHUNK]; };
-    auto issue = [&](Chunk &q, int c) {
-        const int t0 = T - 1 - c * FA_GAEC_CHUNK;
+    if (wave >= 1 && wave <= FA_GAES_LOADERS) {
+        // ---- loaders (every role runs its own copy of the trip loop, each with its own barrier instruction: the counts match,
+        // all from fa_gaes_trips)
+        auto load_chunk = [&](auto who, int c) {
+            constexpr int k0 = decltype(who)::first, n = decltype(who)::n;
+            const int t0 = T - 1 - c * FA_GAEC_CHUNK - k0;  // the loader's first (latest) step
+            float v[n + 1], m[n + 1], r[n];                  // v[i], m[i]: row t0 + 1 - i; r[i]: row t0 - i
+            uint8_t d[n];
 #pragma unroll
-        for (int k = 0; k < FA_GAEC_CHUNK; ++k) {
-            const int t = t0 - k;
-            q.x[k] = ldf(rs_src, coff, (unsigned)(t >= 0 ? t : 0) * rowb);
-        }
-        if (wave == 3) {
-#pragma unroll
-            for (int k = 0; k < FA_GAEC_CHUNK; ++k) {
-                const int t = t0 - k;
-                q.d[k] = __builtin_amdgcn_raw_buffer_load_b8(rs_done, e, __builtin_amdgcn_readfirstlane((int)((unsigned)(t > 0 ? t - 1 : 0) * (unsigned)E)), 0);
+            for (int i = 0; i <= n; ++i) {
+                const int t = t0 + 1 - i;
+                const unsigned so = (unsigned)(t >= 0 ? t : 0) * rowb;
+                v[i] = ldf(rs_val, coff, so);
+                m[i] = ldf(rs_msk, coff, so);
+                if (i < n) {
+                    r[i] = ldf(rs_rew, coff, (unsigned)(t >= 1 ? t - 1 : 0) * rowb);
+                    d[i] = __builtin_amdgcn_raw_buffer_load_b8(rs_done, e, __builtin_amdgcn_readfirstlane((int)((unsigned)(t >= 2 ? t - 2 : 0) * (unsigned)E)), 0);
+                }
             }
-        }
-    };
-    auto stash = [&](const Chunk &q, int c) {
-        float(*dst)[64] = s_x[wave - 1][c & 1];
+            const int b3 = c % 3, b2 = c & 1;
 #pragma unroll
-        for (int k = 0; k < FA_GAEC_CHUNK; ++k) dst[k][lane] = q.x[k];
-        if (wave == 3) {
+            for (int i = 0; i < n; ++i) {
+                const int t = t0 - i;
+                const float delta = r[i] + g32 * v[i] * m[i] - v[i + 1];
+                s_g[b3][k0 + i][lane] = delta;
+                s_c[b2][k0 + i][lane] = gt32 * m[i];
+                s_v[b3][k0 + i][lane] = v[i + 1];
+                s_f[b3][k0 + i][lane] = t < 0 ? FA_GAES_BELOW : (((t > 0) & (d[i] != 0)) ? FA_GAES_STALE : FA_GAES_LIVE);
+            }
+        };
+        auto run = [&](auto who) {
+            for (int j = 0; j < trips; ++j) {
+                const int c = fa_gaes_load_chunk(j, nc);
+                if (c >= 0) load_chunk(who, c);
+                FA_GAEC_BARRIER();
+            }
+        };
+        static_assert(FA_GAES_LOADERS == 3, "one branch per loader below");
+        if (wave == 1) run(FaGaesLoader<0>());
+        else if (wave == 2) run(FaGaesLoader<1>());
+        else run(FaGaesLoader<2>());
+    } else if (wave == 0) {
+        // ---- the scanning wave: the recurrence and nothing else
+        float gae = 0.0f;
+        for (int j = 0; j < trips; ++j) {
+            const int c = fa_gaes_scan_chunk(j, nc);
+            if (c >= 0) {
+                const int b3 = c % 3, b2 = c & 1;
+                // the chunk comes out of LDS in one batch (a read per scan step would put an LDS round
+                // trip on every step of the chain); steps below t = 0 in the last chunk run on clamped rows, behind every real one
+                float dl[FA_GAEC_CHUNK], cc[FA_GAEC_CHUNK];
+                uint8_t f[FA_GAEC_CHUNK];
 #pragma unroll
-            for (int k = 0; k < FA_GAEC_CHUNK; ++k) s_d[c & 1][k][lane] = q.d[k];
+                for (int k = 0; k < FA_GAEC_CHUNK; ++k) { dl[k] = s_g[b3][k][lane]; cc[k] = s_c[b2][k][lane]; f[k] = s_f[b3][k][lane]; }
+#pragma unroll
+                for (int k = 0; k < FA_GAEC_CHUNK; ++k) {
+                    const float g = dl[k] + cc[k] * gae;
+                    s_g[b3][k][lane] = g;
+                    gae = f[k] != FA_GAES_LIVE ? 0.0f : g;   // a select: the reset is exactly +0.0
+                }
+            }
+            FA_GAEC_BARRIER();
         }
-    };
-    if (wave != 0) {
-        // ---- loaders (the two roles run their own copies of the chunk loop, each with its own barrier instructions:
-        // the counts match)
-        Chunk q;
-        issue(q, 0);
-        stash(q, 0);
-        FA_GAEC_BARRIER(); // chunk 0 is in LDS
-        for (int c = 0; c < nc; ++c) {
-            if (c + 1 < nc) {
-                issue(q, c + 1);
-                stash(q, c + 1);
+    } else if (wave < FA_GAES_LOADERS + 3) {
+        // ---- the store waves: steps k = 2 i + par of the chunk behind the scan
+        const int par = wave - (FA_GAES_LOADERS + 1);
+        for (int j = 0; j < trips; ++j) {
+            const int c = fa_gaes_post_chunk(j, nc);
+            if (c >= 0) {
+                const int t0 = T - 1 - c * FA_GAEC_CHUNK - par, b3 = c % 3;
+                float g[FA_GAEC_CHUNK / 2], v[FA_GAEC_CHUNK / 2];
+                uint8_t f[FA_GAEC_CHUNK / 2];
+#pragma unroll
+                for (int i = 0; i < FA_GAEC_CHUNK / 2; ++i) {
+                    g[i] = s_g[b3][2 * i + par][lane]; v[i] = s_v[b3][2 * i + par][lane]; f[i] = s_f[b3][2 * i + par][lane];
+                }
+#pragma unroll
+                for (int i = 0; i < FA_GAEC_CHUNK / 2; ++i) {
+                    const int t = t0 - 2 * i;   // f == 0 implies t >= 0
+                    const float ret = g[i] + v[i];
+                    if (valid & (f[i] == FA_GAES_LIVE)) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ret), rs_ret, (int)coff, __builtin_amdgcn_readfirstlane((int)((unsigned)t * rowb)), 0);
+                }
             }
             FA_GAEC_BARRIER();
         }
     } else {
-        // ---- the scanning wave
-        float gae = 0.0f;
-        float v_next = value_preds[(long long)T * EN + col];
-        float m_next = masks[(long long)T * EN + col];
-        double accS[2] = {0.0, 0.0}, accQ[2] = {0.0, 0.0};
-        const double piv = (double)fa_gae_pivot(rewards, value_preds, masks, T, EN, (int)(col % N), g32);
-        auto add_stale = [&](float o, float v) {
-            const double dd = (double)(o - v) - piv;
-            accS[0] += dd;
-            accQ[0] = __fma_rn(dd, dd, accQ[0]);
-        };
-        float go[FA_GAEC_GATHER], gv[FA_GAEC_GATHER]; // the previous chunk's requested stale entries: old returns, value_preds
-        unsigned gmask = 0u;                            // ... which of them are real
+        // ---- the moment waves: accumulator pair `par` of the one-wave form, i.e. the steps k = 2 i + par in descending t; pair 0
+        // also takes the stale entries.  A skipped step adds +0.0 to S and fma(0, 0, Q) to Q: neither changes a bit (the sums start at
+        // +0.0 and never become -0.0), so the chain has no branch.
+        auto run = [&](auto parity) {
+            constexpr int par = decltype(parity)::value;
+            double accS = 0.0, accQ = 0.0;
+            const double piv = (double)fa_gae_pivot(rewards, value_preds, masks, T, EN, (int)(col % N), g32);
+            auto add_stale = [&](float o, float v) {
+                const double dd = (double)(o - v) - piv;
+                accS += dd;
+                accQ = __fma_rn(dd, dd, accQ);
+            };
+            float go[FA_GAEC_GATHER], gv[FA_GAEC_GATHER]; // the previous chunk's requested stale entries: old returns, value_preds
+            unsigned gmask = 0u;                            // ... which of them are real
 #pragma unroll
-        for (int j = 0; j < FA_GAEC_GATHER; ++j) { go[j] = 0.0f; gv[j] = 0.0f; }
-        FA_GAEC_BARRIER(); // chunk 0 is in LDS
-        auto scan_chunk = [&](int c) {
-            const int t0 = T - 1 - c * FA_GAEC_CHUNK, b = c & 1;
+            for (int j = 0; j < FA_GAEC_GATHER; ++j) { go[j] = 0.0f; gv[j] = 0.0f; }
+            for (int j = 0; j < trips; ++j) {
+                const int c = fa_gaes_post_chunk(j, nc);
+                if (c >= 0) {
+                    const int t0 = T - 1 - c * FA_GAEC_CHUNK, b3 = c % 3;
+                    if (par == 0) {
 #pragma unroll
-            for (int j = 0; j < FA_GAEC_GATHER; ++j)   // requested behind the previous chunk's scan: a barrier's time to arrive
-                if ((gmask >> j) & 1u) add_stale(go[j], gv[j]);
-            // the chunk comes out of LDS in one batch (a read per scan step would put an LDS round
-            // trip on every step of the chain)
-            float r[FA_GAEC_CHUNK], v[FA_GAEC_CHUNK], m[FA_GAEC_CHUNK];
-            uint8_t d[FA_GAEC_CHUNK];
-#pragma unroll
-            for (int k = 0; k < FA_GAEC_CHUNK; ++k) {
-                r[k] = s_x[0][b][k][lane]; v[k] = s_x[1][b][k][lane]; m[k] = s_x[2][b][k][lane]; d[k] = s_d[b][k][lane];
-            }
-            unsigned stale = 0u;
-#pragma unroll
-            for (int k = 0; k < FA_GAEC_CHUNK; ++k) {
-                const int t = t0 - k;
-                if (t >= 0) {
-                    const float delta = r[k] + g32 * v_next * m_next - v[k];
-                    const float g = delta + gt32 * m_next * gae;
-                    if ((t > 0) & (d[k] != 0)) {
-                        gae = 0.0f;
-                        stale |= 1u << k;
-                    } else {
-                        gae = g;
-                        const float ret = g + v[k];
-                        if (valid) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ret), rs_ret, (int)coff, __builtin_amdgcn_readfirstlane((int)((unsigned)t * rowb)), 0);
-                        const double dd = (double)(ret - v[k]) - piv;
-                        accS[k & 1] += dd;
-                        accQ[k & 1] = __fma_rn(dd, dd, accQ[k & 1]);
+                        for (int q = 0; q < FA_GAEC_GATHER; ++q)   // requested behind the previous chunk: a barrier's time to arrive
+                            if ((gmask >> q) & 1u) add_stale(go[q], gv[q]);
                     }
-                    v_next = v[k];
-                    m_next = m[k];
-                }
-            }
-            {
-                // the chunk's stale entries (a few per cent of all): old returns and value_preds straight from memory.  The
-                // first FA_GAEC_GATHER per lane are only REQUESTED here and added at the top of the next chunk -- the raw barrier
-                // leaves them in flight, and waiting for them here would hold the whole workgroup's barrier back by a memory
-                // round trip per chunk (20.4 us for the kernel instead of 17) -- the rest (rare) in a loop on the spot.
-                unsigned rem = stale;
-                gmask = 0u;
+                    float g[FA_GAEC_CHUNK / 2], v[FA_GAEC_CHUNK / 2];
+                    uint8_t f[FA_GAEC_CHUNK];
 #pragma unroll
-                for (int j = 0; j < FA_GAEC_GATHER; ++j) {
-                    const int k = rem ? __builtin_ctz(rem) : 0;
-                    gmask |= (rem ? 1u : 0u) << j;
-                    rem &= rem - 1u;
-                    const unsigned o = (unsigned)(t0 - k) * rowb + coff; // t0 - k >= 1 for a stale k, t0 >= 0 otherwise
-                    go[j] = ldf(rs_ret, o, 0u);
-                    gv[j] = ldf(rs_val, o, 0u);
+                    for (int i = 0; i < FA_GAEC_CHUNK / 2; ++i) { g[i] = s_g[b3][2 * i + par][lane]; v[i] = s_v[b3][2 * i + par][lane]; }
+#pragma unroll
+                    for (int k = 0; k < FA_GAEC_CHUNK; ++k) f[k] = (par == 0 || (k & 1) == par) ? s_f[b3][k][lane] : 0;
+#pragma unroll
+                    for (int i = 0; i < FA_GAEC_CHUNK / 2; ++i) {
+                        const float ret = g[i] + v[i];
+                        const double d0 = (double)(ret - v[i]) - piv;
+                        const double dd = f[2 * i + par] == FA_GAES_LIVE ? d0 : 0.0;
+                        accS += dd;
+                        accQ = __fma_rn(dd, dd, accQ);
+                    }
+                    if (par == 0) {
+                        // the chunk's stale entries (a few per cent of all): old returns and value_preds straight from memory.  The
+                        // first FA_GAEC_GATHER per lane are only REQUESTED here and added at the top of the next chunk -- the raw barrier
+                        // leaves them in flight, and waiting for them here would hold the whole workgroup's barrier back by a memory
+                        // round trip per chunk -- the rest (rare) in a loop on the spot.
+                        unsigned rem = 0u;
+#pragma unroll
+                        for (int k = 0; k < FA_GAEC_CHUNK; ++k) rem |= (f[k] == FA_GAES_STALE ? 1u : 0u) << k;
+                        gmask = 0u;
+#pragma unroll
+                        for (int q = 0; q < FA_GAEC_GATHER; ++q) {
+                            const int k = rem ? __builtin_ctz(rem) : 0;
+                            gmask |= (rem ? 1u : 0u) << q;
+                            rem &= rem - 1u;
+                            const unsigned o = (unsigned)(t0 - k) * rowb + coff; // t0 - k >= 1 for a stale k, t0 >= 0 otherwise
+                            go[q] = ldf(rs_ret, o, 0u);
+                            gv[q] = ldf(rs_val, o, 0u);
+                        }
+                        while (__builtin_amdgcn_ballot_w64(rem != 0u) != 0ull) {
+                            const bool has = rem != 0u;
+                            const int k = has ? __builtin_ctz(rem) : 0;
+                            rem &= rem - 1u;
+                            const unsigned o = (unsigned)(t0 - k) * rowb + coff;
+                            const float o_ = ldf(rs_ret, o, 0u), v_ = ldf(rs_val, o, 0u);
+                            if (has) add_stale(o_, v_);
+                        }
+                    }
                 }
-                while (__builtin_amdgcn_ballot_w64(rem != 0u) != 0ull) {
-                    const bool has = rem != 0u;
-                    const int k = has ? __builtin_ctz(rem) : 0;
-                    rem &= rem - 1u;
-                    const unsigned o = (unsigned)(t0 - k) * rowb + coff;
-                    const float o_ = ldf(rs_ret, o, 0u), v_ = ldf(rs_val, o, 0u);
-                    if (has) add_stale(o_, v_);
-                }
+                FA_GAEC_BARRIER();
             }
+            if (par == 0) {
+#pragma unroll
+                for (int q = 0; q < FA_GAEC_GATHER; ++q)   // the last chunk's
+                    if ((gmask >> q) & 1u) add_stale(go[q], gv[q]);
+            }
+            s_sq[par][0][lane] = valid ? accS : 0.0;
+            s_sq[par][1][lane] = valid ? accQ : 0.0;
         };
-        for (int c = 0; c < nc; ++c) {
-            scan_chunk(c);
-            FA_GAEC_BARRIER();
-        }
-#pragma unroll
-        for (int j = 0; j < FA_GAEC_GATHER; ++j)   // the last chunk's
-            if ((gmask >> j) & 1u) add_stale(go[j], gv[j]);
-        s_sq[0][lane] = valid ? accS[0] + accS[1] : 0.0;
-        s_sq[1][lane] = valid ? accQ[0] + accQ[1] : 0.0;
+        if (wave == FA_GAES_LOADERS + 3) run(FaGaesParity<0>());
+        else run(FaGaesParity<1>());
     }
     {
         __syncthreads();
@@ -367,7 +462,7 @@ __global__ __launch_bounds__(256, 2) void fa_gae_mom_kernel(const float *__restr
             const int i = threadIdx.x >> 1, cmp = threadIdx.x & 1;
             const int first = (int)(((long long)blockIdx.x * 64) % N); // agent of lane 0
             double acc = 0.0;
-            for (int l = (i - first + N) % N; l < 64; l += N) acc += s_sq[cmp][l];
+            for (int l = (i - first + N) % N; l < 64; l += N) acc += s_sq[0][cmp][l] + s_sq[1][cmp][l];
             partial[((long long)blockIdx.x * N + i) * 2 + cmp] = acc;
         }
     }
@@ -930,9 +1025,10 @@ hipError_t fa_launch_gae(const float *rewards, const float *value_preds, const f
 }
 
 // ---- GAE + moments (fa_gae_mom_kernel) and its two possible second launches ---------------------------
-// Eligible up to 512 workgroups = 32 768 (env, agent) columns -- two workgroups per CU.  (Beyond that a CU hosts three and
-// the scanning wave, which carries the fp64 sums and the gathers, falls behind its loaders: 41 us against 34 for the
-// separate kernels at 5v5 x 4096 and 3v3 x 8192; at 3v3 x 4096 / x 1024: 23.7 against 26.0 / 19.0 against 22.1.)  `partial`
+// Eligible up to 512 workgroups = 32 768 (env, agent) columns -- two workgroups per CU, which is what the kernel's 72 KB of
+// LDS admit: beyond that the workgroups of a CU would run one after the other.  (The one-wave form of round 4 to 6, 53 KB,
+// lost there with three per CU: 41 us against 34 for the separate kernels at 5v5 x 4096 and 3v3 x 8192; the role-split
+// kernel was not measured beyond 512.)  At 3v3 x 4096 the fused tail takes 23.7 us against 33.7 for the separate kernels.  `partial`
 // (partial_cap doubles) holds a {S, Q} pair per (workgroup, agent).  Returns the number of workgroups or 0.
 int fa_gae_mom_blocks(const float *rewards, const float *value_preds, const float *masks, const float *returns, int T, int E,
                       int N, long long partial_cap) {
@@ -945,7 +1041,7 @@ int fa_gae_mom_blocks(const float *rewards, const float *value_preds, const floa
 hipError_t fa_launch_gae_mom(const float *rewards, const float *value_preds, const float *masks, float *returns,
                              const uint8_t *done, int T, int E, int N, double gamma, double tau, double *partial, int nblocks,
                              hipStream_t st) {
-    hipLaunchKernelGGL(fa_gae_mom_kernel, dim3(nblocks), dim3(256), 0, st, rewards, value_preds, masks, returns, done, T, E, N,
+    hipLaunchKernelGGL(fa_gae_mom_kernel, dim3(nblocks), dim3(FA_GAES_THREADS), 0, st, rewards, value_preds, masks, returns, done, T, E, N,
                        (float)gamma, (float)(gamma * tau), partial);
     return hipGetLastError();
 }
