@@ -17,3 +17,5 @@ __all__ = ["BatchedFortAttack", "FortAttackGlobalEnv", "make_fortattack_env", "J
            "RolloutStorage", "FaError", "Box", "Discrete", "MASpace", "MPNN", "BatchedLearner", "Neo", "JointPPO",
            "CrossPlay", "crossplay_cells", "crossplay_rows"]
 from . import render  # noqa: F401
+from . import record  # noqa: F401
+from .record import EpisodeRecorder, split_episodes  # noqa: F401

@@ -49,6 +49,12 @@ class PolicyIO(C.Structure):
                 ("guard_pool", c_p), ("guard_pool_size", C.c_int32), ("env_guard_strategy", c_p)]   # appended: offsets above stay
 
 
+class RenderIO(C.Structure):
+    _fields_ = [("env_index", c_p), ("rgb", c_p), ("num_frames", C.c_int32), ("size", C.c_int32), ("actions", c_p),
+                ("act_stride_env", C.c_int64), ("act_stride_agent", C.c_int64), ("no_laser", c_p),
+                ("team_attn", c_p), ("opp_attn", c_p), ("viz_dead", C.c_int32), ("viz_attn", C.c_int32)]
+
+
 class PPOGradIO(C.Structure):
     _fields_ = [("obs", c_p), ("action", c_p), ("value_pred", c_p), ("ret", c_p), ("old_log_prob", c_p), ("adv", c_p),
                 ("idx", c_p), ("weights", c_p), ("weights_t", c_p), ("scale", c_p), ("slabs", c_p), ("hsave", c_p), ("out", c_p),
@@ -108,6 +114,7 @@ EXPORTS = {
     "fa_match_begin": (C.c_int, [c_p, c_p, C.c_int32, C.c_int32, c_p]),
     "fa_match_latch": (C.c_int, [c_p, c_p]),
     "fa_match_table": (C.c_int, [c_p, c_p, C.POINTER(C.c_int32), c_p]),
+    "fa_render": (C.c_int, [c_p, C.POINTER(RenderIO), c_p]),
     "fa_policy_weight_floats": (C.c_int64, []),
     "fa_policy_plain_floats": (C.c_int64, []),
     "fa_attend_forward": (C.c_int, [c_p, c_p, c_p, c_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_p]),

@@ -71,10 +71,13 @@ class CrossPlay(object):
     """CrossPlay(eng, guard_policies, attacker_policies, episodes_per_env): run() plays episodes_per_env episodes on every env
     of `eng` (a BatchedFortAttack with track_counters), env e in cell crossplay_cells(...)[e]; table() is the
     (n_guard, n_attacker, 8) matrix of reference rows, raw() the device sums they come from (add the raw() of shards or
-    ranks to merge them).  Sampling (deterministic=False) is the reference's evaluation mode: Learner.act samples."""
+    ranks to merge them).  Sampling (deterministic=False) is the reference's evaluation mode: Learner.act samples.
+    recorder: a record.EpisodeRecorder over some of the handle's envs (record_envs() picks them; it may also be assigned to
+    `.recorder` before begin()): every step's frames are drawn on the device -- inside the chunk's graph when use_graph is
+    set -- and brought to the host once per chunk.  What is played does not depend on it."""
 
     def __init__(self, eng, guard_policies, attacker_policies, episodes_per_env, num_steps=None, deterministic=False,
-                 sample_seed=0, use_graph=False):
+                 sample_seed=0, use_graph=False, recorder=None):
         self.eng, self.device = eng, eng.device
         self.E, self.G, self.A, self.N = eng.E, eng.G, eng.A, eng.N
         if not eng.cfg.track_counters:
@@ -102,14 +105,26 @@ class CrossPlay(object):
         self.steps_run = 0
         self.remaining = self.E
         self.on_chunk = None        # optional callable(self) after every chunk, before after_update (the storage is whole)
+        self.recorder = recorder
+        self._attn_out = None       # the step's attention maps, exported only for a recorder that draws them
+
+    def record_envs(self, per_cell=1):
+        """The first `per_cell` env indices of every match-up cell, in cell order (a cell with fewer envs gives what it has):
+        the envs an EpisodeRecorder of this evaluation would watch."""
+        cell = self.cell.cpu().numpy()
+        return np.concatenate([np.nonzero(cell == c)[0][:int(per_cell)] for c in range(self.n_cells)]).astype(np.int64)
 
     # ---- one chunk -----------------------------------------------------------------------------------------------
     def _step(self, s):
+        rec = self.recorder
+        attn_out = self._attn_out if rec is not None else None
         self.eng.collect_act(s, None, None, self.sample_seed, self._counter, deterministic=self.deterministic,
                              pool=self.attacker_pool, env_strategy=self.attacker_id,
-                             guard_pool=self.guard_pool, env_guard_strategy=self.guard_id)
+                             guard_pool=self.guard_pool, env_guard_strategy=self.guard_id, attn_out=attn_out)
         self.eng.collect_step(s, auto_reset=True)
         self.eng.match_latch()
+        if rec is not None:
+            rec.capture(s, self.storage, attn_out)
 
     def _warm_state(self):
         """A harmless world for the capture warm-up step (as BatchedLearner._warm_state): teams on opposite walls facing away
@@ -126,7 +141,8 @@ class CrossPlay(object):
         self.storage.obs[:2] = torch.from_numpy(obs.astype(np.float32)).to(self.device)
 
     def _capture(self):
-        """ONE hipGraph for a chunk: T x (act with both pools, env step, latch).  Every launch argument is a fixed pointer."""
+        """ONE hipGraph for a chunk: T x (act with both pools, env step, latch[, the recorder's frames]).  Every launch argument
+        is a fixed pointer."""
         if self.eng.max_time_steps < 8:
             raise ValueError("use_graph needs max_time_steps >= 8 (the warm-up step must not end an episode)")
         self._warm_state()
@@ -145,12 +161,20 @@ class CrossPlay(object):
         return g
 
     def begin(self):
-        """fa_match_begin + a reset of every env (obs[0] <- the reset observations)."""
+        """fa_match_begin + a reset of every env (obs[0] <- the reset observations); with a recorder, its reset frame.  (run()
+        also hands every chunk to the recorder; a caller that drives run_chunk() itself calls recorder.end_chunk(storage).)"""
+        rec = self.recorder
+        if rec is not None and rec.T != self.T:
+            raise ValueError("CrossPlay: the recorder's num_steps (%d) must be the chunk length (%d)" % (rec.T, self.T))
+        if rec is not None and rec.viz_attn and self._attn_out is None:
+            self._attn_out = self.eng.new_attn_out()        # fixed buffers, allocated before any capture
         self.eng.match_begin(self.cell, self.n_cells, self.episodes_per_env)
         if self.use_graph and self._graph is None:
             self._graph = self._capture()
             self.eng.match_begin(self.cell, self.n_cells, self.episodes_per_env)   # the warm-up step is no part of the match
         self.eng.collect_reset()
+        if rec is not None:
+            rec.capture_reset()
         self.steps_run, self.remaining = 0, self.E
 
     def run_chunk(self):
@@ -173,6 +197,8 @@ class CrossPlay(object):
         limit = self.episodes_per_env * self.eng.max_time_steps
         while True:
             rem = self.run_chunk()
+            if self.recorder is not None:
+                self.recorder.end_chunk(self.storage)
             if self.on_chunk is not None:
                 self.on_chunk(self)
             if rem == 0:

@@ -11,6 +11,7 @@
 #include "experiments/fa_step_experiments.h"
 #include "fa_policy.h"
 #include "fa_match.h"
+#include "fa_render.h"
 #include "fa_train.h"
 #include "fortattack.h"
 
@@ -766,6 +767,50 @@ int fa_match_table(fa_env *env, double *raw, int32_t *remaining_out, void *strea
     if (flags[1])
         return fail(FA_ERR_STATE, "fa_match_table: an env played beyond episodes_per_env before it was latched "
                                   "(fa_match_latch must follow every one-step launch)");
+    return FA_OK;
+}
+
+// ---- frames on the device (fa_render.hip) --------------------------------------------------------------
+int fa_render(fa_env *env, const fa_render_io *io, void *stream) {
+    if (!env || !io) return fail(FA_ERR_INVALID, "fa_render: null argument");
+    if (!io->env_index || !io->rgb) return fail(FA_ERR_INVALID, "fa_render: env_index and rgb are required");
+    if (io->num_frames < 1) return fail(FA_ERR_INVALID, "fa_render: num_frames must be >= 1");
+    if (io->size < 8 || io->size > 2048) return fail(FA_ERR_INVALID, "fa_render: size must be 8..2048");
+    if ((io->team_attn != nullptr) != (io->opp_attn != nullptr))
+        return fail(FA_ERR_INVALID, "fa_render: team_attn and opp_attn go together (the guards' pair, or neither)");
+    if ((long long)io->num_frames * fa_render_tiles(io->size) > 0x7fffffffLL)
+        return fail(FA_ERR_INVALID, "fa_render: num_frames x size is more than one launch covers");
+    DeviceGuard guard(env->cfg.device_id);
+    FaRenderArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.s = env->s;
+    a.env_index = io->env_index;
+    a.rgb = io->rgb;
+    a.actions = io->actions;
+    a.as_e = io->act_stride_env;
+    a.as_i = io->act_stride_agent;
+    a.no_laser = io->no_laser;
+    a.team_attn = io->team_attn;
+    a.opp_attn = io->opp_attn;
+    a.K = io->num_frames;
+    a.size = io->size;
+    a.E = env->cfg.num_envs;
+    a.G = env->cfg.num_guards;
+    a.A = env->cfg.num_attackers;
+    a.viz_dead = io->viz_dead != 0;
+    a.attn_on = io->team_attn && io->viz_attn != 0;
+    const FaDerived &c = env->c;
+    a.agent_size = c.agent_size;
+    a.fort_dim = c.fort_dim;
+    a.door_x = c.door_x;
+    a.door_y = c.door_y;
+    a.wall_xmin = c.wall_xmin;
+    a.wall_xmax = c.wall_xmax;
+    a.wall_ymin = c.wall_ymin;
+    a.wall_ymax = c.wall_ymax;
+    a.shoot_rad = c.shoot_rad;
+    a.half_win = c.half_win;
+    FA_HIP(fa_launch_render(a, static_cast<hipStream_t>(stream)));
     return FA_OK;
 }
 

@@ -361,6 +361,47 @@ class BatchedFortAttack(object):
         _lib.check(self._lib.fa_match_table(self._h, _ptr(out), C.byref(rem), _stream()), "fa_match_table")
         return out, int(rem.value)
 
+    # -- frames on the device (csrc/fa_render.hip) ------------------------------------------------
+    def render(self, env_index, size=350, actions=None, no_laser=None, attn=None, viz_dead=False, viz_attn=True, out=None):
+        """fa_render: frame k = env env_index[k] drawn from the device state -> uint8 (K, size, size, 3) on the device, row 0 at
+        the top; the picture (and, operation for operation, the arithmetic) of render.render_frame.  env_index: a list, a numpy
+        array (range-checked here, ValueError) or a device int32 tensor (used as is -- an entry outside [0, E) leaves its frame
+        untouched).  actions: int64 (E, N) device tensor of any strides (storage.actions[s] as it is): a laser where the value
+        is 7, except in the envs flagged by no_laser (E) uint8 (storage.done[s]: after an auto-reset the state is the next
+        episode's).  attn = (team, opp): the guards' maps, attn_out[0] of policy_act / collect_act.  With device tensors for
+        env_index and `out` the call allocates nothing and can be captured in a graph."""
+        if not torch.is_tensor(env_index):
+            idx = np.asarray(env_index)
+            if idx.ndim != 1 or idx.size < 1 or idx.dtype.kind not in "iu":
+                raise ValueError("render: env_index must be a non-empty 1-d integer sequence")
+            if int(idx.min()) < 0 or int(idx.max()) >= self.E:
+                raise ValueError("render: env_index must lie in [0, %d), got %d .. %d" % (self.E, int(idx.min()), int(idx.max())))
+            env_index = torch.from_numpy(idx.astype(np.int32)).to(self.device)
+        assert env_index.is_cuda and env_index.dtype == torch.int32 and env_index.dim() == 1 and env_index.is_contiguous()
+        K, size = int(env_index.numel()), int(size)
+        if out is None:
+            out = self._new((K, size, size, 3), torch.uint8)
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (K, size, size, 3)
+        io = _lib.RenderIO()
+        io.env_index, io.rgb, io.num_frames, io.size = _ptr(env_index), _ptr(out), K, size
+        if actions is not None:
+            if actions.dim() == 3 and actions.shape[-1] == 1:      # a row of JointRolloutStorage.actions: (E, N, 1)
+                actions = actions[..., 0]
+            assert actions.is_cuda and actions.dtype == torch.int64 and tuple(actions.shape) == (self.E, self.N)
+            io.actions, io.act_stride_env, io.act_stride_agent = _ptr(actions), actions.stride(0), actions.stride(1)
+        if no_laser is not None:
+            assert no_laser.is_cuda and no_laser.dtype == torch.uint8 and no_laser.is_contiguous() and no_laser.numel() == self.E
+            io.no_laser = _ptr(no_laser)
+        if attn is not None:
+            team, opp = attn
+            for buf, shape in zip((team, opp), self.attn_shapes()[0]):
+                assert (buf.is_cuda and buf.dtype == torch.float32 and buf.is_contiguous() and
+                        tuple(buf.shape) == shape), "attn: the guards' float32 contiguous %s expected" % (shape,)
+            io.team_attn, io.opp_attn = _ptr(team), _ptr(opp)
+        io.viz_dead, io.viz_attn = int(bool(viz_dead)), int(bool(viz_attn))
+        _lib.check(self._lib.fa_render(self._h, C.byref(io), _stream()), "fa_render")
+        return out
+
     # -- state snapshot ----------------------------------------------------------------
     _F64 = ("pos_x", "pos_y", "vel_x", "vel_y", "ang", "prev_dist")
 

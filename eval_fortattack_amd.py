@@ -12,6 +12,10 @@ Writes to --out-dir:
   reward_data_ensemble.npy                    only with --num-eval-episodes 1: (guard ckpts, K x episodes, 1 + N), column 0
                                               the guard checkpoint, then every agent's episode return
                                               (test_fortattack_v2_gen_plot_data.py:55,117-118)
+  video_g<guard>_a<attacker>_env<e>_ep<i>.gif only with --record: the first --record-episodes episodes of the first
+                                              --record-per-cell envs of every match-up, --record-size pixels a side, drawn on
+                                              the device with the guards' attention (test_fortattack.py --render --record
+                                              --video-format gif); .npz (array ep0) with --video-format npz
 
 Differences from the reference scripts: --num-eval-episodes counts episodes PER ENV (every match-up is played by
 num-processes / (guards x attackers) envs, so it gets that many times as many episodes); --guard-ckpts names the series
@@ -37,7 +41,17 @@ def get_args(argv=None):
     p.add_argument("--deterministic", action="store_true", help="argmax actions (the reference samples)")
     p.add_argument("--no-graph", action="store_true", help="do not replay the chunk from a hipGraph")
     p.add_argument("--out-dir", default=None, help="default: --guard-load-dir")
-    return p.parse_args(argv)
+    p.add_argument("--record", action="store_true", help="write one video per recorded episode of every match-up")
+    p.add_argument("--video-format", choices=["gif", "npz"], default="gif")
+    p.add_argument("--record-size", type=int, default=128, help="frame side in pixels")
+    p.add_argument("--record-per-cell", type=int, default=1, help="envs recorded per match-up")
+    p.add_argument("--record-episodes", type=int, default=1, help="episodes recorded per env (<= --num-eval-episodes)")
+    args = p.parse_args(argv)
+    if args.record and not 1 <= args.record_episodes <= args.num_eval_episodes:
+        p.error("--record-episodes must be 1 .. --num-eval-episodes (%d)" % args.num_eval_episodes)
+    if args.record and args.record_per_cell < 1:
+        p.error("--record-per-cell must be >= 1")
+    return args
 
 
 def main():
@@ -75,6 +89,9 @@ def main():
                 finished.logical_or_(done)
                 running[done] = 0.0
         cp.on_chunk = on_chunk
+    if args.record:
+        rec_envs = cp.record_envs(args.record_per_cell)
+        cp.recorder = fa.EpisodeRecorder(eng, rec_envs, cp.T, size=args.record_size)
     cp.run()
     raw = cp.raw().cpu().numpy()
     table = cp.table()
@@ -92,6 +109,17 @@ def main():
             for i in range(K):
                 data[k, i * per_cell:(i + 1) * per_cell, 1:] = ret[cell == k * K + i][:per_cell]
         np.save(os.path.join(out_dir, "reward_data_ensemble"), data)
+    if args.record:
+        cell = cp.cell.cpu().numpy()
+        for e, episodes in zip(rec_envs, cp.recorder.episodes(args.record_episodes)):
+            g, a = divmod(int(cell[e]), K)
+            for i, frames in enumerate(episodes):
+                path = os.path.join(out_dir, "video_g%d_a%d_env%d_ep%d.%s" % (args.guard_ckpts[g], args.attacker_ckpts[a], e, i,
+                                                                              args.video_format))
+                if args.video_format == "gif":
+                    fa.record.write_gif(path, frames)
+                else:
+                    fa.record.write_npz(path, [frames])
     np.set_printoptions(suppress=True, precision=4)
     for k, ck in enumerate(args.guard_ckpts):
         print("guard checkpoint %d" % ck)

@@ -345,6 +345,33 @@ int fa_match_begin(fa_env *env, const int32_t *env_cell, int32_t n_cells, int32_
 int fa_match_latch(fa_env *env, void *stream);
 int fa_match_table(fa_env *env, double *raw, int32_t *remaining_out, void *stream);
 
+/* ---- frames on the device ----------------------------------------------------------------------------
+ * replaces FortAttackGlobalEnv.render (fortattack.py:368-600; the scene :420-560, the attention discs :439-466 and the
+ * reference agent's dot :531-546, camera bounds +-1 :582-587) for K frames in one launch: frame k shows env env_index[k] of
+ * the handle, drawn from the handle's own device state -- no host copy -- as uint8 RGB, row 0 at the top.  The picture and
+ * its arithmetic are those of the package's numpy rasteriser (render.py render_frame): white background, black active
+ * region, fort disc, laser triangles (alpha 0.3) of the alive agents whose action is 7, yellow attention discs of radius
+ * agent_size * (1 + w), body and head discs, the reference agent's half-colour dot, grey strips.  The reference agent is the
+ * first agent that is alive or is the last guard; w is the weight it gives the drawn agent in the guards' maps.
+ * All pointers are device pointers and fixed: the launch neither allocates nor synchronises, so it can be captured in a
+ * hipGraph behind the step that produced the state.  An env_index entry outside [0, E) leaves its frame untouched. */
+typedef struct fa_render_io {
+    const int32_t *env_index;  /* (K) */
+    uint8_t *rgb;              /* (K, size, size, 3) */
+    int32_t num_frames;        /* K >= 1 */
+    int32_t size;              /* 8 .. 2048 pixels per side */
+    const int64_t *actions;    /* or NULL: element (e,i) at actions[e*act_stride_env + i*act_stride_agent], as in
+                                  fa_step_io (a row storage.actions[s] can be passed as is); a laser where the value is 7 */
+    int64_t act_stride_env, act_stride_agent;
+    const uint8_t *no_laser;   /* (E) or NULL: an env whose flag is set draws no lasers -- pass the step's `done` row, after
+                                  an auto-reset the state already belongs to the next episode */
+    const float *team_attn;    /* the GUARDS' maps of fa_policy_io: team_attn[0] (E, G, G) and opp_attn[0] (E, G, A); */
+    const float *opp_attn;     /* both or neither */
+    int32_t viz_dead;          /* != 0: dead agents are drawn translucent (fortattack.py:468-470) */
+    int32_t viz_attn;          /* != 0 and maps given: attention discs and the dot */
+} fa_render_io;
+int fa_render(fa_env *env, const fa_render_io *io, void *stream);
+
 /* number of floats of one team's packed weight buffer; of its leading float32 sections (= a plain-layout buffer) */
 int64_t fa_policy_weight_floats(void);
 int64_t fa_policy_plain_floats(void);
