@@ -26,7 +26,7 @@ def needs_build():
         return False
     if not os.path.isfile(LIB):
         return True
-    deps = [os.path.join(CSRC, f) for f in SOURCES + ["fa_device.h", "fa_step_common.h", "experiments/fa_step_experiments.h", "fa_probe.h", "fa_policy.h", "fa_match.h", "fa_render.h", "fa_mfma.h", "fa_train.h"]]
+    deps = [os.path.join(CSRC, f) for f in SOURCES + ["fa_device.h", "fa_step_common.h", "experiments/fa_step_experiments.h", "fa_probe.h", "fa_policy.h", "fa_match.h", "fa_render.h", "fa_mfma.h", "fa_train.h", "fa_collect.h"]]
     deps.append(os.path.join(ROOT, "include", "fortattack.h"))
     return any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps)
 

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "fa_device.h"
+#include "fa_collect.h"
 #include "experiments/fa_step_experiments.h"
 #include "fa_policy.h"
 #include "fa_match.h"
@@ -23,35 +24,8 @@ hipError_t fa_launch_seed(const FaState &s, int E, uint64_t base_seed, int64_t e
                           hipStream_t st);
 hipError_t fa_launch_selftest(unsigned long long n_per_thread, unsigned long long seed, unsigned long long *mismatch,
                               hipStream_t st);
-hipError_t fa_launch_gae(const float *rewards, const float *value_preds, const float *masks, float *returns,
-                         const uint8_t *done, int T, int E, int N, double gamma, double tau, hipStream_t st);
-int fa_gae_mom_blocks(const float *rewards, const float *value_preds, const float *masks, const float *returns, int T, int E,
-                      int N, long long partial_cap);
-hipError_t fa_launch_gae_mom(const float *rewards, const float *value_preds, const float *masks, float *returns,
-                             const uint8_t *done, int T, int E, int N, double gamma, double tau, double *partial, int nblocks,
-                             hipStream_t st);
-hipError_t fa_launch_gae_mom_final(const double *partial, int nblocks, const float *rewards, const float *value_preds,
-                                   const float *masks, int T, int E, int N, double gamma, double *moments_out, double *mean_out,
-                                   double *std_out, hipStream_t st);
-hipError_t fa_launch_gae_mom_norm(const double *partial, int nblocks, const float *rewards, const float *value_preds,
-                                  const float *masks, const float *returns, int T, int E, int N, double gamma, float *out,
-                                  double *moments_out, double *mean_out, double *std_out, int grid, int piv_from_returns,
-                                  hipStream_t st);
-hipError_t fa_launch_adv_merge_norm(const double *gathered, int W, int N, const float *returns, const float *value_preds,
-                                    long long total, float *out, double *mean_out, double *std_out, hipStream_t st);
-hipError_t fa_launch_adv_onepass(const float *returns, const float *value_preds, long long rows, int N, double *partial,
-                                 int nblocks, double *moments_out, double *mean_out, double *std_out, hipStream_t st,
-                                 bool final = true);
-hipError_t fa_launch_adv_stats(int pass, const float *returns, const float *value_preds, const double *mean,
-                               long long rows, int N, double *partial, int nblocks, double *stats,
-                               double *derived, hipStream_t st);
-hipError_t fa_launch_adv_merge(const double *gathered, int W, int N, double *mean_out, double *std_out,
-                               hipStream_t st);
-hipError_t fa_launch_adv_moments_fix(double *stats, int N, hipStream_t st);
 hipError_t fa_launch_attend(int width, bool backward, const float *g, const float *keys, float *out, float *attn,
                             const float *dout, float *dg, float *dkeys, int B, int n, int nk, int skip_self, hipStream_t st);
-hipError_t fa_launch_adv_norm(const float *returns, const float *value_preds, const double *mean,
-                              const double *std_, long long total, int N, float *out, hipStream_t st);
 
 static thread_local std::string g_err;
 
@@ -182,6 +156,57 @@ FaStepArgs base_args(const fa_env *env) {
     a.c = env->c;
     a.nsteps = 1;
     return a;
+}
+
+// The bound storage as the collector tail's launchers take it (fa_collect.h); gamma, gamma * tau rounded to float32 once.
+FaTailArgs tail_args(const fa_env *env, double gamma = 0.0, double tau = 0.0) {
+    const fa_storage &st = env->st;
+    FaTailArgs a;
+    a.rewards = st.rewards;
+    a.value_preds = st.value_preds;
+    a.masks = st.masks;
+    a.returns = st.returns;
+    a.done = st.done;
+    a.T = st.num_steps;
+    a.E = env->cfg.num_envs;
+    a.N = env->N;
+    a.g32 = (float)gamma;
+    a.gt32 = (float)(gamma * tau);
+    return a;
+}
+
+// How the tail is launched for the bound storage: the workgroup count of every grid that depends on the shape alone.
+struct FaTailPlan {
+    int fused;   // fa_gae_mom_kernel's workgroups; 0: the shape is beyond the fused scan, the separate kernels serve
+    int sweep;   // fa_adv_onepass[_vec]_kernel
+    int twopass; // fa_adv_partial[_vec]_kernel
+};
+FaTailPlan tail_plan(const fa_env *env, const FaTailArgs &a) {
+    FaTailPlan p;
+    p.fused = fa_gae_mom_blocks(a.T, a.E, a.N, (long long)env->adv_blocks * FA_MAX_AGENTS * 2);
+    // a lane takes 2 rows x 4 per trip: one workgroup per 2048 rows, at most two per CU (512: what the fold takes)
+    long long want = (a.rows() + 2047) / 2048;
+    p.sweep = (int)(want < 512 ? (want < 1 ? 1 : want) : 512);
+    // a row per lane and trip, as many workgroups as adv_partial holds
+    want = (a.rows() + 255) / 256;
+    p.twopass = (int)(want < env->adv_blocks ? want : env->adv_blocks);
+    return p;
+}
+
+// The scan and the {S, Q} partials of the advantage moments in env->adv_partial: the fused scan where it serves, else fa_gae
+// and the one-pass sweep.  Returns where the partials come from and how many workgroups wrote them; the caller folds them
+// (fa_launch_gae_mom_final) or folds and normalises (fa_launch_gae_mom_norm).
+struct FaTailPartials {
+    hipError_t err;
+    FaStatSource src;
+    int count;
+};
+FaTailPartials tail_scan_partials(const fa_env *env, const FaTailArgs &a, hipStream_t s) {
+    const FaTailPlan p = tail_plan(env, a);
+    if (p.fused) return {fa_launch_gae_mom(a, env->adv_partial, p.fused, s), FA_STATS_SCAN_PARTIALS, p.fused};
+    hipError_t e = fa_launch_gae(a, s);
+    if (e == hipSuccess) e = fa_launch_adv_onepass(a, env->adv_partial, p.sweep, s);
+    return {e, FA_STATS_SWEEP_PARTIALS, p.sweep};
 }
 } // namespace
 
@@ -467,20 +492,8 @@ int fa_gae(fa_env *env, double gamma, double tau, void *stream) {
     if (!env) return fail(FA_ERR_INVALID, "fa_gae: null env");
     if (!env->bound) return fail(FA_ERR_STATE, "fa_gae: no storage bound");
     DeviceGuard guard(env->cfg.device_id);
-    const fa_storage &st = env->st;
-    FA_HIP(fa_launch_gae(st.rewards, st.value_preds, st.masks, st.returns, st.done, st.num_steps,
-                         env->cfg.num_envs, env->N, gamma, tau, static_cast<hipStream_t>(stream)));
+    FA_HIP(fa_launch_gae(tail_args(env, gamma, tau), static_cast<hipStream_t>(stream)));
     return FA_OK;
-}
-
-// the fused scan's workgroup count for this handle's storage, 0 where the separate kernels serve (see fa_gae_mom_blocks;
-// FA_GAE_MOMENTS_SEPARATE=1 in the environment forces them: the A/B switch of tools/ab_tail.py)
-static int gae_mom_blocks(const fa_env *env) {
-    static const bool separate = [] { const char *v = getenv("FA_GAE_MOMENTS_SEPARATE"); return v && v[0] == '1'; }();
-    if (separate) return 0;
-    const fa_storage &st = env->st;
-    return fa_gae_mom_blocks(st.rewards, st.value_preds, st.masks, st.returns, st.num_steps, env->cfg.num_envs, env->N,
-                             (long long)env->adv_blocks * FA_MAX_AGENTS * 2);
 }
 
 int fa_gae_moments(fa_env *env, double gamma, double tau, double *moments_out, double *mean_out, double *std_out,
@@ -488,24 +501,12 @@ int fa_gae_moments(fa_env *env, double gamma, double tau, double *moments_out, d
     if (!env) return fail(FA_ERR_INVALID, "fa_gae_moments: null env");
     if (!env->bound) return fail(FA_ERR_STATE, "fa_gae_moments: no storage bound");
     DeviceGuard guard(env->cfg.device_id);
-    const fa_storage &st = env->st;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (const int nb = gae_mom_blocks(env)) {
-        // two launches: the scan leaves the workgroups' moment partials, one workgroup folds them
-        FA_HIP(fa_launch_gae_mom(st.rewards, st.value_preds, st.masks, st.returns, st.done, st.num_steps, env->cfg.num_envs,
-                                 env->N, gamma, tau, env->adv_partial, nb, s));
-        FA_HIP(fa_launch_gae_mom_final(env->adv_partial, nb, st.rewards, st.value_preds, st.masks, st.num_steps,
-                                       env->cfg.num_envs, env->N, gamma, moments_out, mean_out, std_out, s));
-        return FA_OK;
-    }
-    FA_HIP(fa_launch_gae(st.rewards, st.value_preds, st.masks, st.returns, st.done, st.num_steps,
-                         env->cfg.num_envs, env->N, gamma, tau, s));
-    const long long rows = (long long)st.num_steps * env->cfg.num_envs;
-    // a lane takes 2 rows x 4 per trip: one workgroup per 2048 rows, at most two per CU
-    long long want = (rows + 2047) / 2048;
-    const int nblocks = (int)(want < 512 ? (want < 1 ? 1 : want) : 512);
-    FA_HIP(fa_launch_adv_onepass(st.returns, st.value_preds, rows, env->N, env->adv_partial, nblocks, moments_out,
-                                 mean_out, std_out, s));
+    const FaTailArgs a = tail_args(env, gamma, tau);
+    // scan + moment partials (two launches beyond the fused scan), then one workgroup folds them
+    const FaTailPartials p = tail_scan_partials(env, a, s);
+    FA_HIP(p.err);
+    FA_HIP(fa_launch_gae_mom_final(a, p.src, env->adv_partial, p.count, moments_out, mean_out, std_out, s));
     return FA_OK;
 }
 
@@ -514,27 +515,13 @@ int fa_gae_normalize(fa_env *env, double gamma, double tau, float *adv_out, doub
     if (!env || !adv_out) return fail(FA_ERR_INVALID, "fa_gae_normalize: null argument");
     if (!env->bound) return fail(FA_ERR_STATE, "fa_gae_normalize: no storage bound");
     DeviceGuard guard(env->cfg.device_id);
-    const fa_storage &st = env->st;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (const int nb = gae_mom_blocks(env)) {
-        // two launches: scan + moment partials; fold + normalisation by every workgroup
-        FA_HIP(fa_launch_gae_mom(st.rewards, st.value_preds, st.masks, st.returns, st.done, st.num_steps, env->cfg.num_envs,
-                                 env->N, gamma, tau, env->adv_partial, nb, s));
-        FA_HIP(fa_launch_gae_mom_norm(env->adv_partial, nb, st.rewards, st.value_preds, st.masks, st.returns, st.num_steps,
-                                      env->cfg.num_envs, env->N, gamma, adv_out, moments_out, mean_out, std_out, 0, 0, s));
-        return FA_OK;
-    }
-    // beyond the fused scan: fa_gae, the one-pass sweep (at most 512 workgroups of partials), and the same fold +
-    // normalisation launch on its partials -- three launches instead of four, nothing dirty left behind the last one
-    FA_HIP(fa_launch_gae(st.rewards, st.value_preds, st.masks, st.returns, st.done, st.num_steps, env->cfg.num_envs, env->N, gamma,
-                         tau, s));
-    const long long rows = (long long)st.num_steps * env->cfg.num_envs;
-    long long want = (rows + 2047) / 2048;   // as fa_gae_moments
-    const int nblocks = (int)(want < 512 ? (want < 1 ? 1 : want) : 512);
-    FA_HIP(fa_launch_adv_onepass(st.returns, st.value_preds, rows, env->N, env->adv_partial, nblocks, nullptr, nullptr, nullptr, s,
-                                 false));
-    FA_HIP(fa_launch_gae_mom_norm(env->adv_partial, nblocks, st.rewards, st.value_preds, st.masks, st.returns, st.num_steps,
-                                  env->cfg.num_envs, env->N, gamma, adv_out, moments_out, mean_out, std_out, 0, 1, s));
+    const FaTailArgs a = tail_args(env, gamma, tau);
+    // scan + moment partials; fold + normalisation by every workgroup -- two launches, three beyond the fused scan (instead
+    // of four), nothing dirty left behind the last one
+    const FaTailPartials p = tail_scan_partials(env, a, s);
+    FA_HIP(p.err);
+    FA_HIP(fa_launch_gae_mom_norm(a, p.src, env->adv_partial, p.count, adv_out, moments_out, mean_out, std_out, s));
     return FA_OK;
 }
 
@@ -542,12 +529,12 @@ int fa_adv_moments_onepass(fa_env *env, double *moments_out, double *mean_out, d
     if (!env) return fail(FA_ERR_INVALID, "fa_adv_moments_onepass: null env");
     if (!env->bound) return fail(FA_ERR_STATE, "fa_adv_moments_onepass: no storage bound");
     DeviceGuard guard(env->cfg.device_id);
-    const fa_storage &st = env->st;
-    const long long rows = (long long)st.num_steps * env->cfg.num_envs;
-    long long want = (rows + 2047) / 2048;   // as fa_gae_moments: a lane takes 2 rows x 4 per trip, at most two workgroups per CU
-    const int nblocks = (int)(want < 512 ? (want < 1 ? 1 : want) : 512);
-    FA_HIP(fa_launch_adv_onepass(st.returns, st.value_preds, rows, env->N, env->adv_partial, nblocks, moments_out, mean_out,
-                                 std_out, static_cast<hipStream_t>(stream)));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const FaTailArgs a = tail_args(env);
+    const int nblocks = tail_plan(env, a).sweep;
+    FA_HIP(fa_launch_adv_onepass(a, env->adv_partial, nblocks, s));
+    FA_HIP(fa_launch_gae_mom_final(a, FA_STATS_SWEEP_PARTIALS, env->adv_partial, nblocks, moments_out, mean_out,
+                                   std_out, s));
     return FA_OK;
 }
 
@@ -557,12 +544,9 @@ int fa_adv_stats(fa_env *env, int32_t pass, const double *mean, double *stats, v
     if (pass != 0 && pass != 1) return fail(FA_ERR_INVALID, "fa_adv_stats: pass must be 0 or 1");
     if (pass == 1 && !mean) return fail(FA_ERR_INVALID, "fa_adv_stats: pass 1 needs mean");
     DeviceGuard guard(env->cfg.device_id);
-    const fa_storage &st = env->st;
-    const long long rows = (long long)st.num_steps * env->cfg.num_envs;
-    long long want = (rows + 255) / 256;
-    const int nblocks = (int)(want < env->adv_blocks ? want : env->adv_blocks);
-    FA_HIP(fa_launch_adv_stats(pass, st.returns, st.value_preds, mean, rows, env->N, env->adv_partial,
-                               nblocks, stats, nullptr, static_cast<hipStream_t>(stream)));
+    const FaTailArgs a = tail_args(env);
+    FA_HIP(fa_launch_adv_stats(pass, a.returns, a.value_preds, mean, a.rows(), a.N, env->adv_partial,
+                               tail_plan(env, a).twopass, stats, nullptr, static_cast<hipStream_t>(stream)));
     return FA_OK;
 }
 
@@ -570,14 +554,12 @@ int fa_adv_mean_std(fa_env *env, double *mean_out, double *std_out, void *stream
     if (!env || !mean_out || !std_out) return fail(FA_ERR_INVALID, "fa_adv_mean_std: null argument");
     if (!env->bound) return fail(FA_ERR_STATE, "fa_adv_mean_std: no storage bound");
     DeviceGuard guard(env->cfg.device_id);
-    const fa_storage &st = env->st;
-    const long long rows = (long long)st.num_steps * env->cfg.num_envs;
-    long long want = (rows + 255) / 256;
-    const int nblocks = (int)(want < env->adv_blocks ? want : env->adv_blocks);
+    const FaTailArgs a = tail_args(env);
+    const int nblocks = tail_plan(env, a).twopass;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    FA_HIP(fa_launch_adv_stats(0, st.returns, st.value_preds, nullptr, rows, env->N, env->adv_partial, nblocks,
+    FA_HIP(fa_launch_adv_stats(0, a.returns, a.value_preds, nullptr, a.rows(), a.N, env->adv_partial, nblocks,
                                env->adv_stats, mean_out, s));
-    FA_HIP(fa_launch_adv_stats(1, st.returns, st.value_preds, mean_out, rows, env->N, env->adv_partial, nblocks,
+    FA_HIP(fa_launch_adv_stats(1, a.returns, a.value_preds, mean_out, a.rows(), a.N, env->adv_partial, nblocks,
                                env->adv_stats, std_out, s));
     return FA_OK;
 }
@@ -586,17 +568,15 @@ int fa_adv_moments(fa_env *env, double *moments_out, void *stream) {
     if (!env || !moments_out) return fail(FA_ERR_INVALID, "fa_adv_moments: null argument");
     if (!env->bound) return fail(FA_ERR_STATE, "fa_adv_moments: no storage bound");
     DeviceGuard guard(env->cfg.device_id);
-    const fa_storage &st = env->st;
-    const long long rows = (long long)st.num_steps * env->cfg.num_envs;
-    long long want = (rows + 255) / 256;
-    const int nblocks = (int)(want < env->adv_blocks ? want : env->adv_blocks);
+    const FaTailArgs a = tail_args(env);
+    const int nblocks = tail_plan(env, a).twopass;
     hipStream_t s = static_cast<hipStream_t>(stream);
     double *mean = env->adv_stats + 3 * FA_MAX_AGENTS; // scratch: local mean
-    FA_HIP(fa_launch_adv_stats(0, st.returns, st.value_preds, nullptr, rows, env->N, env->adv_partial, nblocks,
+    FA_HIP(fa_launch_adv_stats(0, a.returns, a.value_preds, nullptr, a.rows(), a.N, env->adv_partial, nblocks,
                                moments_out, mean, s));
-    FA_HIP(fa_launch_adv_stats(1, st.returns, st.value_preds, mean, rows, env->N, env->adv_partial, nblocks,
+    FA_HIP(fa_launch_adv_stats(1, a.returns, a.value_preds, mean, a.rows(), a.N, env->adv_partial, nblocks,
                                moments_out, nullptr, s));
-    FA_HIP(fa_launch_adv_moments_fix(moments_out, env->N, s));
+    FA_HIP(fa_launch_adv_moments_fix(moments_out, a.N, s));
     return FA_OK;
 }
 
@@ -615,10 +595,8 @@ int fa_adv_merge_normalize(fa_env *env, const double *gathered, int32_t world, f
     if (world < 1) return fail(FA_ERR_INVALID, "fa_adv_merge_normalize: world must be >= 1");
     if (!env->bound) return fail(FA_ERR_STATE, "fa_adv_merge_normalize: no storage bound");
     DeviceGuard guard(env->cfg.device_id);
-    const fa_storage &st = env->st;
-    const long long total = (long long)st.num_steps * env->cfg.num_envs * env->N;
-    FA_HIP(fa_launch_adv_merge_norm(gathered, world, env->N, st.returns, st.value_preds, total, adv_out, mean_out, std_out,
-                                    static_cast<hipStream_t>(stream)));
+    FA_HIP(fa_launch_gae_mom_norm(tail_args(env), FA_STATS_GATHERED_RANKS, gathered, world, adv_out, nullptr, mean_out,
+                                  std_out, static_cast<hipStream_t>(stream)));
     return FA_OK;
 }
 
@@ -626,10 +604,7 @@ int fa_adv_normalize(fa_env *env, const double *mean, const double *std_, float 
     if (!env || !mean || !std_ || !adv_out) return fail(FA_ERR_INVALID, "fa_adv_normalize: null argument");
     if (!env->bound) return fail(FA_ERR_STATE, "fa_adv_normalize: no storage bound");
     DeviceGuard guard(env->cfg.device_id);
-    const fa_storage &st = env->st;
-    const long long total = (long long)st.num_steps * env->cfg.num_envs * env->N;
-    FA_HIP(fa_launch_adv_norm(st.returns, st.value_preds, mean, std_, total, env->N, adv_out,
-                              static_cast<hipStream_t>(stream)));
+    FA_HIP(fa_launch_adv_norm(tail_args(env), mean, std_, adv_out, static_cast<hipStream_t>(stream)));
     return FA_OK;
 }
 

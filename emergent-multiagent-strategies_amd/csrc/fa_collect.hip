@@ -6,6 +6,7 @@
 // (t, e, i); the statistics read ret, V (8 B).  One lane per column, consecutive lanes
 // on consecutive columns => every row access is a coalesced span.
 #include "fa_device.h"
+#include "fa_collect.h"
 
 // Learner.wrap_horizon (learner.py:191-211) + RolloutStorage.compute_returns
 // (storage.py:59-66) as one backward pass with per-env episode boundaries.
@@ -15,6 +16,15 @@
 // and the accumulator restarts at 0 for the segment below it.
 // float32 throughout, operation order of storage.py:63-66; gamma and gamma*tau are
 // rounded to float32 once (torch scalar * tensor).
+// The one definition of a scan step, used by all four scans (and fa_gae_pivot):
+//   delta_t = r + g32 * v_next * m_next - v   and   c_t = gt32 * m_next   depend on the inputs alone,
+//   g_t = delta_t + c_t * gae                 is the recurrence; at an episode end the accumulator restarts at +0.0.
+__device__ __forceinline__ float fa_gae_delta(float r, float v, float v_next, float m_next, float g32) {
+    return r + g32 * v_next * m_next - v;
+}
+__device__ __forceinline__ float fa_gae_c(float m_next, float gt32) { return gt32 * m_next; }
+__device__ __forceinline__ float fa_gae_step(float delta, float c, float gae) { return delta + c * gae; }
+
 #define FA_GAE_CHUNK 16
 struct FaGaeChunk { float r[FA_GAE_CHUNK], v[FA_GAE_CHUNK], m[FA_GAE_CHUNK]; uint8_t d[FA_GAE_CHUNK]; };
 __global__ __launch_bounds__(64) void fa_gae_kernel(const float *__restrict__ rewards,
@@ -51,8 +61,8 @@ __global__ __launch_bounds__(64) void fa_gae_kernel(const float *__restrict__ re
         for (int k = 0; k < FA_GAE_CHUNK; ++k) {
             const int t = t0 - k;
             if (t >= 0) {
-                const float delta = c.r[k] + g32 * v_next * m_next - c.v[k];
-                const float g = delta + gt32 * m_next * gae;
+                const float delta = fa_gae_delta(c.r[k], c.v[k], v_next, m_next, g32);
+                const float g = fa_gae_step(delta, fa_gae_c(m_next, gt32), gae);
                 if ((t > 0) & (c.d[k] != 0)) {
                     gae = 0.0f;
                 } else {
@@ -151,8 +161,8 @@ __global__ __launch_bounds__(256) void fa_gae_coop_kernel(const float *__restric
             for (int k = 0; k < FA_GAEC_CHUNK; ++k) {
                 const int t = t0 - k;
                 if (t >= 0) {
-                    const float delta = r[k] + g32 * v_next * m_next - v[k];
-                    const float g = delta + gt32 * m_next * gae;
+                    const float delta = fa_gae_delta(r[k], v[k], v_next, m_next, g32);
+                    const float g = fa_gae_step(delta, fa_gae_c(m_next, gt32), gae);
                     if ((t > 0) & (d[k] != 0)) {
                         gae = 0.0f;
                     } else {
@@ -214,8 +224,16 @@ __device__ __forceinline__ float fa_gae_pivot(const float *__restrict__ rewards,
                                               const float *__restrict__ masks, int T, long long EN, int i, float g32) {
     const long long o = (long long)(T - 1) * EN + i, o1 = (long long)T * EN + i;
     const float vp = value_preds[o];
-    const float delta = rewards[o] + g32 * value_preds[o1] * masks[o1] - vp;
+    const float delta = fa_gae_delta(rewards[o], vp, value_preds[o1], masks[o1], g32);
     return (delta + vp) - vp;
+}
+// The one-pass accumulation around a pivot, used by the moment waves and by the fa_adv_onepass*_kernel sweeps: the deviation
+// of a float32 advantage (returns - value_preds, subtracted in float32 as the reference does) from the pivot, S += dd,
+// Q = fma(dd, dd, Q), all in fp64.
+__device__ __forceinline__ double fa_mom_dev(float adv, double piv) { return (double)adv - piv; }
+__device__ __forceinline__ void fa_mom_add(double dd, double &S, double &Q) {
+    S += dd;
+    Q = __fma_rn(dd, dd, Q);
 }
 
 // The roles' shared arithmetic.  Loader l owns the steps k in [fa_gaes_first(l), fa_gaes_first(l + 1)) of every chunk.
@@ -312,9 +330,8 @@ __global__ __launch_bounds__(FA_GAES_THREADS) void fa_gae_mom_kernel(const float
 #pragma unroll
             for (int i = 0; i < n; ++i) {
                 const int t = t0 - i;
-                const float delta = r[i] + g32 * v[i] * m[i] - v[i + 1];
-                s_g[b3][k0 + i][lane] = delta;
-                s_c[b2][k0 + i][lane] = gt32 * m[i];
+                s_g[b3][k0 + i][lane] = fa_gae_delta(r[i], v[i + 1], v[i], m[i], g32);   // v[i], m[i]: the step's v_next, m_next
+                s_c[b2][k0 + i][lane] = fa_gae_c(m[i], gt32);
                 s_v[b3][k0 + i][lane] = v[i + 1];
                 s_f[b3][k0 + i][lane] = t < 0 ? FA_GAES_BELOW : (((t > 0) & (d[i] != 0)) ? FA_GAES_STALE : FA_GAES_LIVE);
             }
@@ -345,7 +362,7 @@ __global__ __launch_bounds__(FA_GAES_THREADS) void fa_gae_mom_kernel(const float
                 for (int k = 0; k < FA_GAEC_CHUNK; ++k) { dl[k] = s_g[b3][k][lane]; cc[k] = s_c[b2][k][lane]; f[k] = s_f[b3][k][lane]; }
 #pragma unroll
                 for (int k = 0; k < FA_GAEC_CHUNK; ++k) {
-                    const float g = dl[k] + cc[k] * gae;
+                    const float g = fa_gae_step(dl[k], cc[k], gae);
                     s_g[b3][k][lane] = g;
                     gae = f[k] != FA_GAES_LIVE ? 0.0f : g;   // a select: the reset is exactly +0.0
                 }
@@ -383,9 +400,8 @@ __global__ __launch_bounds__(FA_GAES_THREADS) void fa_gae_mom_kernel(const float
             double accS = 0.0, accQ = 0.0;
             const double piv = (double)fa_gae_pivot(rewards, value_preds, masks, T, EN, (int)(col % N), g32);
             auto add_stale = [&](float o, float v) {
-                const double dd = (double)(o - v) - piv;
-                accS += dd;
-                accQ = __fma_rn(dd, dd, accQ);
+                const double dd = fa_mom_dev(o - v, piv);
+                fa_mom_add(dd, accS, accQ);
             };
             float go[FA_GAEC_GATHER], gv[FA_GAEC_GATHER]; // the previous chunk's requested stale entries: old returns, value_preds
             unsigned gmask = 0u;                            // ... which of them are real
@@ -409,10 +425,9 @@ __global__ __launch_bounds__(FA_GAES_THREADS) void fa_gae_mom_kernel(const float
 #pragma unroll
                     for (int i = 0; i < FA_GAEC_CHUNK / 2; ++i) {
                         const float ret = g[i] + v[i];
-                        const double d0 = (double)(ret - v[i]) - piv;
+                        const double d0 = fa_mom_dev(ret - v[i], piv);
                         const double dd = f[2 * i + par] == FA_GAES_LIVE ? d0 : 0.0;
-                        accS += dd;
-                        accQ = __fma_rn(dd, dd, accQ);
+                        fa_mom_add(dd, accS, accQ);
                     }
                     if (par == 0) {
                         // the chunk's stale entries (a few per cent of all): old returns and value_preds straight from memory.  The
@@ -496,14 +511,47 @@ __device__ __forceinline__ void fa_gae_mom_fold(const double *__restrict__ parti
     m2 = q - s * (s / n_rows);
 }
 
+// The pivot the partials were accumulated around.  piv_from_returns = 0: fa_gae_mom_kernel's, from the scan's inputs;
+// 1: fa_adv_onepass[_vec]_kernel's (shapes beyond the fused scan), agent i's advantage in row 0 AFTER the scan.
+__device__ __forceinline__ double fa_row0_pivot(const float *__restrict__ returns, const float *__restrict__ value_preds, int i) {
+    return (double)(returns[i] - value_preds[i]);
+}
+__device__ __forceinline__ double fa_partials_pivot(int piv_from_returns, const float *__restrict__ rewards,
+                                                    const float *__restrict__ value_preds, const float *__restrict__ masks,
+                                                    const float *__restrict__ returns, int T, long long EN, int i, float g32) {
+    return piv_from_returns ? fa_row0_pivot(returns, value_preds, i)
+                            : (double)fa_gae_pivot(rewards, value_preds, masks, T, EN, i, g32);
+}
+
+// Chan-Golub-LeVeque merge of agent i's per-rank (n, mean, M2) triples in rank order: exact combination of two-pass
+// statistics, the same bits on every rank and in every workgroup.  gathered: (W, N, 3).
+__device__ __forceinline__ void fa_merge_ranks(const double *__restrict__ gathered, int W, int N, int i, double &n, double &mean,
+                                               double &m2) {
+    n = 0.0; mean = 0.0; m2 = 0.0;
+    for (int r = 0; r < W; ++r) {
+        const double *g = gathered + ((long long)r * N + i) * 3;
+        const double nr = g[0], mr = g[1], m2r = g[2];
+        if (nr <= 0.0) continue;
+        const double nn = n + nr, delta = mr - mean;
+        mean += delta * (nr / nn);
+        m2 += m2r + delta * delta * (n * nr / nn);
+        n = nn;
+    }
+}
+
+// ppo.py:123: (A - mean) / (std + 1e-5), float32 arithmetic with float32 mean / std; A = returns - value_preds in float32.
+__device__ __forceinline__ float fa_norm_den(double sd) { return (float)sd + 1e-5f; }
+__device__ __forceinline__ float fa_norm_adv(float ret, float v, float mean, float den) { return (ret - v - mean) / den; }
+
+// One workgroup folds the partials of the fused scan or of the one-pass sweep (piv_from_returns, see fa_partials_pivot).
 __global__ void fa_gae_mom_final_kernel(const double *__restrict__ partial, int nblocks, int N,
                                         const float *__restrict__ rewards, const float *__restrict__ value_preds,
-                                        const float *__restrict__ masks, int T, long long EN, float g32, double n_rows,
-                                        double *__restrict__ moments_out, double *__restrict__ mean_out,
-                                        double *__restrict__ std_out) {
+                                        const float *__restrict__ masks, const float *__restrict__ returns, int T, long long EN,
+                                        float g32, double n_rows, double *__restrict__ moments_out,
+                                        double *__restrict__ mean_out, double *__restrict__ std_out, int piv_from_returns) {
     const int i = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (i >= N) return;
-    const double piv = (double)fa_gae_pivot(rewards, value_preds, masks, T, EN, i, g32);
+    const double piv = fa_partials_pivot(piv_from_returns, rewards, value_preds, masks, returns, T, EN, i, g32);
     double mean, m2;
     fa_gae_mom_fold(partial, nblocks, N, i, lane, n_rows, piv, mean, m2);
     if (lane == 0) {
@@ -515,8 +563,9 @@ __global__ void fa_gae_mom_final_kernel(const double *__restrict__ partial, int 
 
 // The fold and ppo.py:123 in one launch (one rank: nothing is exchanged between them): every workgroup
 // folds the partials itself -- one wave per agent, 6 KB per agent out of L2 at config 2 -- and normalises its
-// share of the advantages, 16 bytes per lane and trip, the first trip requested ahead of the fold.  (A - (float)mean) / ((float)std + 1e-5f) as fa_adv_norm_kernel; workgroup 0
-// also leaves moments / mean / std.  `total` = T*E*N.
+// share of the advantages, 16 bytes per lane and trip, the first trip requested ahead of the fold.  The normalising expression
+// is fa_adv_norm_kernel's (fa_norm_adv); workgroup 0 also leaves moments / mean / std.  `total` = T*E*N.
+// The statistics come from one of three sources, named on the host by FaStatSource (fa_launch_gae_mom_norm).
 __global__ __launch_bounds__(512) void fa_gae_mom_norm_kernel(const double *__restrict__ partial, int nblocks, int N,
                                                               const float *__restrict__ rewards,
                                                               const float *__restrict__ value_preds,
@@ -527,9 +576,8 @@ __global__ __launch_bounds__(512) void fa_gae_mom_norm_kernel(const double *__re
                                                               double *__restrict__ std_out, int piv_from_returns,
                                                               const double *__restrict__ gathered, int W) {
     // gathered != null (several ranks): no fold -- every workgroup merges the W ranks' (n, mean, M2) triples as fa_adv_merge_kernel
-    // does (one lane per agent, rank order: same bits everywhere) and normalises with the result.
-    // piv_from_returns: the partials are fa_adv_onepass[_vec]_kernel's (shapes beyond the fused scan), whose pivot is agent i's
-    // advantage in row 0 AFTER the scan; same {S, Q} layout, same fold as fa_adv_onepass_final_kernel: same bits
+    // does (one lane per agent, fa_merge_ranks) and normalises with the result.
+    // piv_from_returns: the partials are the one-pass sweep's; same {S, Q} layout, same fold (fa_partials_pivot)
     __shared__ float s_mean[FA_MAX_AGENTS_DEV], s_den[FA_MAX_AGENTS_DEV];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long stride = (long long)gridDim.x * blockDim.x;
@@ -547,19 +595,11 @@ __global__ __launch_bounds__(512) void fa_gae_mom_norm_kernel(const double *__re
     if (gathered) {
         if ((int)threadIdx.x < N) {
             const int i = threadIdx.x;
-            double n = 0.0, mean = 0.0, m2 = 0.0;
-            for (int r = 0; r < W; ++r) { // Chan-Golub-LeVeque in rank order: fa_adv_merge_kernel's loop
-                const double *g = gathered + ((long long)r * N + i) * 3;
-                const double nr = g[0], mr = g[1], m2r = g[2];
-                if (nr <= 0.0) continue;
-                const double nn = n + nr, delta = mr - mean;
-                mean += delta * (nr / nn);
-                m2 += m2r + delta * delta * (n * nr / nn);
-                n = nn;
-            }
+            double n, mean, m2;
+            fa_merge_ranks(gathered, W, N, i, n, mean, m2);
             const double sd = sqrt(m2 / (n - 1.0));
             s_mean[i] = (float)mean;
-            s_den[i] = (float)sd + 1e-5f;
+            s_den[i] = fa_norm_den(sd);
             if (blockIdx.x == 0) {
                 if (mean_out) mean_out[i] = mean;
                 if (std_out) std_out[i] = sd;
@@ -567,14 +607,13 @@ __global__ __launch_bounds__(512) void fa_gae_mom_norm_kernel(const double *__re
         }
     } else
     for (int i = wave; i < N; i += 8) { // eight waves: one agent each up to 4v4, one round trip
-        const double piv = piv_from_returns ? (double)(returns[i] - value_preds[i])
-                                            : (double)fa_gae_pivot(rewards, value_preds, masks, T, EN, i, g32);
+        const double piv = fa_partials_pivot(piv_from_returns, rewards, value_preds, masks, returns, T, EN, i, g32);
         double mean, m2;
         fa_gae_mom_fold(partial, nblocks, N, i, lane, n_rows, piv, mean, m2);
         const double sd = sqrt(m2 / (n_rows - 1.0));
         if (lane == 0) {
             s_mean[i] = (float)mean;
-            s_den[i] = (float)sd + 1e-5f;
+            s_den[i] = fa_norm_den(sd);
             if (blockIdx.x == 0) {
                 if (moments_out) { moments_out[i * 3 + 0] = n_rows; moments_out[i * 3 + 1] = mean; moments_out[i * 3 + 2] = m2; }
                 if (mean_out) mean_out[i] = mean;
@@ -585,7 +624,6 @@ __global__ __launch_bounds__(512) void fa_gae_mom_norm_kernel(const double *__re
     __syncthreads();
     if (vec) {
         float4 *o4 = reinterpret_cast<float4 *>(out);
-#ifndef FA_NORM_PLAIN_STORES
         // write-through (sc1) 16-byte stores: nothing of `out` stays dirty in L2 for the kernel boundary behind this launch to
         // flush (29.4 against 30.1 us for the two launches, 177.4 against 178.4 behind the rollout; 16-byte sc1 stores cost what
         // plain ones do -- the 8-byte observation rows of the step kernel as sc1 stores: slower, 180.0 against 177.8)
@@ -600,9 +638,6 @@ __global__ __launch_bounds__(512) void fa_gae_mom_norm_kernel(const double *__re
                 o4[q] = v;
             }
         };
-#else
-        auto st4 = [&](long long q, const float4 &v) { o4[q] = v; };
-#endif
         for (long long q0 = gid; q0 < quads; q0 += 2 * stride) {
             const long long q1 = q0 + stride;
             const bool two = q1 < quads;
@@ -613,10 +648,10 @@ __global__ __launch_bounds__(512) void fa_gae_mom_norm_kernel(const double *__re
             auto norm4 = [&](const float4 &r, const float4 &v, long long q) {
                 int i = (int)((4 * q) % N);
                 float4 o;
-                o.x = (r.x - v.x - s_mean[i]) / s_den[i]; i = i + 1 == N ? 0 : i + 1;
-                o.y = (r.y - v.y - s_mean[i]) / s_den[i]; i = i + 1 == N ? 0 : i + 1;
-                o.z = (r.z - v.z - s_mean[i]) / s_den[i]; i = i + 1 == N ? 0 : i + 1;
-                o.w = (r.w - v.w - s_mean[i]) / s_den[i];
+                o.x = fa_norm_adv(r.x, v.x, s_mean[i], s_den[i]); i = i + 1 == N ? 0 : i + 1;
+                o.y = fa_norm_adv(r.y, v.y, s_mean[i], s_den[i]); i = i + 1 == N ? 0 : i + 1;
+                o.z = fa_norm_adv(r.z, v.z, s_mean[i], s_den[i]); i = i + 1 == N ? 0 : i + 1;
+                o.w = fa_norm_adv(r.w, v.w, s_mean[i], s_den[i]);
                 return o;
             };
             st4(q0, norm4(ra, va, q0));
@@ -624,12 +659,12 @@ __global__ __launch_bounds__(512) void fa_gae_mom_norm_kernel(const double *__re
         }
         for (long long k = quads * 4 + gid; k < total; k += stride) {
             const int i = (int)(k % N);
-            out[k] = (returns[k] - value_preds[k] - s_mean[i]) / s_den[i];
+            out[k] = fa_norm_adv(returns[k], value_preds[k], s_mean[i], s_den[i]);
         }
     } else {
         for (long long k = gid; k < total; k += stride) {
             const int i = (int)(k % N);
-            out[k] = (returns[k] - value_preds[k] - s_mean[i]) / s_den[i];
+            out[k] = fa_norm_adv(returns[k], value_preds[k], s_mean[i], s_den[i]);
         }
     }
 }
@@ -681,8 +716,8 @@ __global__ __launch_bounds__(64) void fa_gae4_kernel(const float *__restrict__ r
                 float *ret = returns + (long long)t * EN + col;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const float delta = rr[q] + g32 * vn[q] * mn[q] - vv[q];
-                    const float g = delta + gt32 * mn[q] * gae[q];
+                    const float delta = fa_gae_delta(rr[q], vv[q], vn[q], mn[q], g32);
+                    const float g = fa_gae_step(delta, fa_gae_c(mn[q], gt32), gae[q]);
                     const bool sk = (skip[k] >> q) & 1u;
                     gae[q] = sk ? 0.0f : g;
                     out[q] = g + vv[q];
@@ -822,38 +857,7 @@ __device__ __forceinline__ void fa_adv_onepass_finish(double (&acc_s)[FA_MAX_AGE
     }
 }
 
-// one wave per agent: lane l takes workgroups l, l+64, ... in order (loads issued together), then a
-// fixed shuffle tree
-#define FA_ADV_FOLD 16 // partial workgroups per lane of the final fold: nblocks <= 64 * FA_ADV_FOLD
-__global__ void fa_adv_onepass_final_kernel(const double *__restrict__ partial, int nblocks, int N,
-                                            const float *__restrict__ returns, const float *__restrict__ value_preds,
-                                            double n_rows, double *__restrict__ moments_out,
-                                            double *__restrict__ mean_out, double *__restrict__ std_out) {
-    const int i = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (i >= N) return;
-    double ps[FA_ADV_FOLD], pq[FA_ADV_FOLD];
-#pragma unroll
-    for (int k = 0; k < FA_ADV_FOLD; ++k) {
-        const int b = lane + 64 * k;
-        const bool in = b < nblocks;
-        const double *p = partial + ((long long)(in ? b : 0) * N + i) * 2;
-        ps[k] = in ? p[0] : 0.0;
-        pq[k] = in ? p[1] : 0.0;
-    }
-    double s = 0.0, q = 0.0;
-#pragma unroll
-    for (int k = 0; k < FA_ADV_FOLD; ++k) { s += ps[k]; q += pq[k]; }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { s += __shfl_down(s, off, 64); q += __shfl_down(q, off, 64); }
-    if (lane == 0) {
-        const double piv = (double)(returns[i] - value_preds[i]); // the pivot of the sweep: row 0
-        const double mean = piv + s / n_rows, m2 = q - s * (s / n_rows);
-        if (moments_out) { moments_out[i * 3 + 0] = n_rows; moments_out[i * 3 + 1] = mean; moments_out[i * 3 + 2] = m2; }
-        if (mean_out) mean_out[i] = mean;
-        if (std_out) std_out[i] = sqrt(m2 / (n_rows - 1.0));
-    }
-}
-
+// (The workgroups' partials are folded by fa_gae_mom_final_kernel or fa_gae_mom_norm_kernel with the row-0 pivot.)
 __global__ __launch_bounds__(256) void fa_adv_onepass_kernel(const float *__restrict__ returns,
                                                              const float *__restrict__ value_preds, long long rows, int N,
                                                              double *__restrict__ partial) {
@@ -861,7 +865,7 @@ __global__ __launch_bounds__(256) void fa_adv_onepass_kernel(const float *__rest
 #pragma unroll
     for (int i = 0; i < FA_MAX_AGENTS_DEV; ++i) {
         acc_s[i] = 0.0; acc_q[i] = 0.0;
-        piv[i] = i < N ? (double)(returns[i] - value_preds[i]) : 0.0;
+        piv[i] = i < N ? fa_row0_pivot(returns, value_preds, i) : 0.0;
     }
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
@@ -869,9 +873,8 @@ __global__ __launch_bounds__(256) void fa_adv_onepass_kernel(const float *__rest
 #pragma unroll
         for (int i = 0; i < FA_MAX_AGENTS_DEV; ++i) {
             if (i < N) {
-                const double d = (double)(ret[i] - vp[i]) - piv[i];
-                acc_s[i] += d;
-                acc_q[i] = __fma_rn(d, d, acc_q[i]);
+                const double d = fa_mom_dev(ret[i] - vp[i], piv[i]);
+                fa_mom_add(d, acc_s[i], acc_q[i]);
             }
         }
     }
@@ -889,7 +892,7 @@ __global__ __launch_bounds__(256) void fa_adv_onepass_vec_kernel(const float *__
 #pragma unroll
     for (int i = 0; i < FA_MAX_AGENTS_DEV; ++i) {
         acc_s[i] = 0.0; acc_q[i] = 0.0;
-        piv[i] = i < TN ? (double)(returns[i] - value_preds[i]) : 0.0;
+        piv[i] = i < TN ? fa_row0_pivot(returns, value_preds, i) : 0.0;
     }
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long p0 = (long long)blockIdx.x * blockDim.x + threadIdx.x; p0 < row_pairs; p0 += stride * UNR) {
@@ -913,9 +916,7 @@ __global__ __launch_bounds__(256) void fa_adv_onepass_vec_kernel(const float *__
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const int i = (4 * q + j) % TN; // folds to a constant after unrolling
-                        const double d = (double)a4[j] - piv[i];
-                        acc_s[i] += d;
-                        acc_q[i] = __fma_rn(d, d, acc_q[i]);
+                        fa_mom_add(fa_mom_dev(a4[j], piv[i]), acc_s[i], acc_q[i]);
                     }
                 }
             }
@@ -955,28 +956,17 @@ __global__ __launch_bounds__(256) void fa_adv_norm_kernel(const float *__restric
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < total; k += stride) {
         const int i = (int)(k % N);
-        const float adv = returns[k] - value_preds[k];
-        out[k] = (adv - (float)mean[i]) / ((float)std_[i] + 1e-5f);
+        out[k] = fa_norm_adv(returns[k], value_preds[k], (float)mean[i], fa_norm_den(std_[i]));
     }
 }
 
-// Chan-Golub-LeVeque merge of per-rank (n, mean, M2) triples in rank order: exact combination
-// of two-pass statistics, identical on every rank, one collective instead of two.
-// gathered: (W, N, 3); one lane per agent.
+// The merge of fa_merge_ranks alone: one collective instead of two.  gathered: (W, N, 3); one lane per agent.
 __global__ void fa_adv_merge_kernel(const double *__restrict__ gathered, int W, int N,
                                     double *__restrict__ mean_out, double *__restrict__ std_out) {
     const int i = threadIdx.x;
     if (i >= N) return;
-    double n = 0.0, mean = 0.0, m2 = 0.0;
-    for (int r = 0; r < W; ++r) {
-        const double *g = gathered + ((long long)r * N + i) * 3;
-        const double nr = g[0], mr = g[1], m2r = g[2];
-        if (nr <= 0.0) continue;
-        const double nn = n + nr, delta = mr - mean;
-        mean += delta * (nr / nn);
-        m2 += m2r + delta * delta * (n * nr / nn);
-        n = nn;
-    }
+    double n, mean, m2;
+    fa_merge_ranks(gathered, W, N, i, n, mean, m2);
     mean_out[i] = mean;
     std_out[i] = sqrt(m2 / (n - 1.0));
 }
@@ -998,29 +988,23 @@ hipError_t fa_launch_adv_moments_fix(double *stats, int N, hipStream_t st) {
     return hipGetLastError();
 }
 
-hipError_t fa_launch_gae(const float *rewards, const float *value_preds, const float *masks, float *returns,
-                         const uint8_t *done, int T, int E, int N, double gamma, double tau, hipStream_t st) {
-    const long long EN = (long long)E * N;
+hipError_t fa_launch_gae(const FaTailArgs &a, hipStream_t st) {
+    const long long EN = (long long)a.E * a.N;
     // four columns per lane pay off only once there are enough columns to fill the chip with
     // 16-byte lanes; below that the one-column kernel has 4x the waves in flight
-    const bool vec4 = (EN >= 4LL * 64 * 1024) && (EN % 4 == 0) && ((((uintptr_t)rewards | (uintptr_t)value_preds | (uintptr_t)masks |
-                                          (uintptr_t)returns) & 15) == 0);
-    if (!vec4 && EN <= 64LL * 2048) {
+    const bool vec4 = (EN >= 4LL * 64 * 1024) && (EN % 4 == 0) && ((((uintptr_t)a.rewards | (uintptr_t)a.value_preds | (uintptr_t)a.masks |
+                                          (uintptr_t)a.returns) & 15) == 0);
+    const int grid = (int)(((vec4 ? EN / 4 : EN) + 63) / 64);   // 64 lanes of one column each, or of four
+    if (vec4)
+        hipLaunchKernelGGL(fa_gae4_kernel, dim3(grid), dim3(64), 0, st, a.rewards, a.value_preds, a.masks, a.returns, a.done, a.T, a.E,
+                           a.N, a.g32, a.gt32);
+    else if (EN <= 64LL * 2048)
         // few columns: four cooperating waves per 64 columns (see fa_gae_coop_kernel)
-        const int grid = (int)((EN + 63) / 64);
-        hipLaunchKernelGGL(fa_gae_coop_kernel, dim3(grid), dim3(256), 0, st, rewards, value_preds, masks, returns,
-                           done, T, E, N, (float)gamma, (float)(gamma * tau));
-        return hipGetLastError();
-    }
-    if (vec4) {
-        const int grid = (int)((EN / 4 + 63) / 64);
-        hipLaunchKernelGGL(fa_gae4_kernel, dim3(grid), dim3(64), 0, st, rewards, value_preds, masks, returns,
-                           done, T, E, N, (float)gamma, (float)(gamma * tau));
-    } else {
-        const int grid = (int)((EN + 63) / 64);
-        hipLaunchKernelGGL(fa_gae_kernel, dim3(grid), dim3(64), 0, st, rewards, value_preds, masks, returns,
-                           done, T, E, N, (float)gamma, (float)(gamma * tau));
-    }
+        hipLaunchKernelGGL(fa_gae_coop_kernel, dim3(grid), dim3(256), 0, st, a.rewards, a.value_preds, a.masks, a.returns, a.done,
+                           a.T, a.E, a.N, a.g32, a.gt32);
+    else
+        hipLaunchKernelGGL(fa_gae_kernel, dim3(grid), dim3(64), 0, st, a.rewards, a.value_preds, a.masks, a.returns, a.done, a.T, a.E,
+                           a.N, a.g32, a.gt32);
     return hipGetLastError();
 }
 
@@ -1030,77 +1014,55 @@ hipError_t fa_launch_gae(const float *rewards, const float *value_preds, const f
 // lost there with three per CU: 41 us against 34 for the separate kernels at 5v5 x 4096 and 3v3 x 8192; the role-split
 // kernel was not measured beyond 512.)  At 3v3 x 4096 the fused tail takes 23.7 us against 33.7 for the separate kernels.  `partial`
 // (partial_cap doubles) holds a {S, Q} pair per (workgroup, agent).  Returns the number of workgroups or 0.
-int fa_gae_mom_blocks(const float *rewards, const float *value_preds, const float *masks, const float *returns, int T, int E,
-                      int N, long long partial_cap) {
+int fa_gae_mom_blocks(int T, int E, int N, long long partial_cap) {
     const long long EN = (long long)E * N;
     if (EN > 64LL * 512 || T < 1 || (long long)(T + 1) * EN * 4 >= (1LL << 31)) return 0;
     const long long nb = (EN + 63) / 64;
     if (nb > 64 * FA_GAEM_FOLD || nb * N * 2 > partial_cap) return 0;
     return (int)nb;
 }
-hipError_t fa_launch_gae_mom(const float *rewards, const float *value_preds, const float *masks, float *returns,
-                             const uint8_t *done, int T, int E, int N, double gamma, double tau, double *partial, int nblocks,
-                             hipStream_t st) {
-    hipLaunchKernelGGL(fa_gae_mom_kernel, dim3(nblocks), dim3(FA_GAES_THREADS), 0, st, rewards, value_preds, masks, returns, done, T, E, N,
-                       (float)gamma, (float)(gamma * tau), partial);
+hipError_t fa_launch_gae_mom(const FaTailArgs &a, double *partial, int nblocks, hipStream_t st) {
+    hipLaunchKernelGGL(fa_gae_mom_kernel, dim3(nblocks), dim3(FA_GAES_THREADS), 0, st, a.rewards, a.value_preds, a.masks, a.returns,
+                       a.done, a.T, a.E, a.N, a.g32, a.gt32, partial);
     return hipGetLastError();
 }
-hipError_t fa_launch_gae_mom_final(const double *partial, int nblocks, const float *rewards, const float *value_preds,
-                                   const float *masks, int T, int E, int N, double gamma, double *moments_out, double *mean_out,
-                                   double *std_out, hipStream_t st) {
-    const long long EN = (long long)E * N;
-    const double n_rows = (double)T * (double)E;
-    hipLaunchKernelGGL(fa_gae_mom_final_kernel, dim3(1), dim3(64 * N), 0, st, partial, nblocks, N, rewards, value_preds, masks, T,
-                       EN, (float)gamma, n_rows, moments_out, mean_out, std_out);
+hipError_t fa_launch_gae_mom_final(const FaTailArgs &a, FaStatSource src, const double *stats, int count, double *moments_out,
+                                   double *mean_out, double *std_out, hipStream_t st) {
+    hipLaunchKernelGGL(fa_gae_mom_final_kernel, dim3(1), dim3(64 * a.N), 0, st, stats, count, a.N, a.rewards, a.value_preds, a.masks,
+                       a.returns, a.T, (long long)a.E * a.N, a.g32, (double)a.T * (double)a.E, moments_out, mean_out,
+                       std_out, src == FA_STATS_SWEEP_PARTIALS ? 1 : 0);
     return hipGetLastError();
 }
-hipError_t fa_launch_gae_mom_norm(const double *partial, int nblocks, const float *rewards, const float *value_preds,
-                                  const float *masks, const float *returns, int T, int E, int N, double gamma, float *out,
-                                  double *moments_out, double *mean_out, double *std_out, int grid, int piv_from_returns,
-                                  hipStream_t st) {
-    const long long EN = (long long)E * N, total = (long long)T * EN;
-    const double n_rows = (double)T * (double)E;
-    if (grid <= 0) {
-        // a lane takes two 16-byte quads per trip; two workgroups of eight waves per CU (measured at config 2's 38 MB:
-        // 128 / 256 / 512 / 1024 workgroups -> 31.6 / 29.7 / 30.0 / 31.6 us for the two launches, 512 the best behind the rollout)
-        long long want = (total / 4 + 1023) / 1024;
-        grid = (int)(want < 512 ? (want < 1 ? 1 : want) : 512);
-    }
-    hipLaunchKernelGGL(fa_gae_mom_norm_kernel, dim3(grid), dim3(512), 0, st, partial, nblocks, N, rewards, value_preds, masks,
-                       returns, T, EN, (float)gamma, n_rows, total, out, moments_out, mean_out, std_out, piv_from_returns,
-                       (const double *)nullptr, 0);
-    return hipGetLastError();
-}
-// several ranks: fa_adv_merge + fa_adv_normalize as ONE launch (every workgroup merges the gathered triples itself)
-hipError_t fa_launch_adv_merge_norm(const double *gathered, int W, int N, const float *returns, const float *value_preds,
-                                    long long total, float *out, double *mean_out, double *std_out, hipStream_t st) {
-    long long want = (total / 4 + 1023) / 1024;
+hipError_t fa_launch_gae_mom_norm(const FaTailArgs &a, FaStatSource src, const double *stats, int count, float *out,
+                                  double *moments_out, double *mean_out, double *std_out, hipStream_t st) {
+    // a lane takes two 16-byte quads per trip; two workgroups of eight waves per CU (measured at config 2's 38 MB:
+    // 128 / 256 / 512 / 1024 workgroups -> 31.6 / 29.7 / 30.0 / 31.6 us for the two launches, 512 the best behind the rollout)
+    const long long want = (a.total() / 4 + 1023) / 1024;
     const int grid = (int)(want < 512 ? (want < 1 ? 1 : want) : 512);
-    hipLaunchKernelGGL(fa_gae_mom_norm_kernel, dim3(grid), dim3(512), 0, st, (const double *)nullptr, 0, N, (const float *)nullptr,
-                       value_preds, (const float *)nullptr, returns, 0, 0LL, 0.0f, 0.0, total, out, (double *)nullptr, mean_out,
-                       std_out, 0, gathered, W);
+    // several ranks: fa_adv_merge + fa_adv_normalize as ONE launch (every workgroup merges the gathered triples itself)
+    const bool merge = src == FA_STATS_GATHERED_RANKS;
+    hipLaunchKernelGGL(fa_gae_mom_norm_kernel, dim3(grid), dim3(512), 0, st, merge ? nullptr : stats, merge ? 0 : count, a.N, a.rewards,
+                       a.value_preds, a.masks, a.returns, a.T, (long long)a.E * a.N, a.g32, (double)a.T * (double)a.E,
+                       a.total(), out, merge ? nullptr : moments_out, mean_out, std_out, src == FA_STATS_SWEEP_PARTIALS ? 1 : 0,
+                       merge ? stats : nullptr, merge ? count : 0);
     return hipGetLastError();
 }
 
-// one-pass moments; `partial` must hold nblocks * N * 2 doubles, nblocks <= 64 * FA_ADV_FOLD
-// (final = false: the sweep alone -- its partials then go to fa_launch_gae_mom_norm(..., piv_from_returns = 1); needs nblocks <=
-// 64 * FA_GAEM_FOLD)
-hipError_t fa_launch_adv_onepass(const float *returns, const float *value_preds, long long rows, int N, double *partial,
-                                 int nblocks, double *moments_out, double *mean_out, double *std_out, hipStream_t st,
-                                 bool final = true) {
-    const bool vec = (rows % 2 == 0) && ((((uintptr_t)returns | (uintptr_t)value_preds) & 15) == 0);
-    if (nblocks > 64 * FA_ADV_FOLD) nblocks = 64 * FA_ADV_FOLD;
-    if (vec && N == 6)
-        hipLaunchKernelGGL((fa_adv_onepass_vec_kernel<6>), dim3(nblocks), dim3(256), 0, st, returns, value_preds, rows / 2,
-                           partial);
-    else if (vec && N == 10)
-        hipLaunchKernelGGL((fa_adv_onepass_vec_kernel<10>), dim3(nblocks), dim3(256), 0, st, returns, value_preds, rows / 2,
-                           partial);
+// The one-pass sweep: `partial` must hold nblocks * N * 2 doubles.  Its partials go to fa_launch_gae_mom_final or
+// fa_launch_gae_mom_norm with FA_STATS_SWEEP_PARTIALS, whose fold takes at most 64 * FA_GAEM_FOLD workgroups.
+hipError_t fa_launch_adv_onepass(const FaTailArgs &a, double *partial, int nblocks, hipStream_t st) {
+    const long long rows = a.rows();
+    const bool vec = (rows % 2 == 0) && ((((uintptr_t)a.returns | (uintptr_t)a.value_preds) & 15) == 0);
+    if (nblocks > 64 * FA_GAEM_FOLD) nblocks = 64 * FA_GAEM_FOLD;
+    if (vec && a.N == 6)
+        hipLaunchKernelGGL((fa_adv_onepass_vec_kernel<6>), dim3(nblocks), dim3(256), 0, st, a.returns, a.value_preds,
+                           rows / 2, partial);
+    else if (vec && a.N == 10)
+        hipLaunchKernelGGL((fa_adv_onepass_vec_kernel<10>), dim3(nblocks), dim3(256), 0, st, a.returns, a.value_preds,
+                           rows / 2, partial);
     else
-        hipLaunchKernelGGL(fa_adv_onepass_kernel, dim3(nblocks), dim3(256), 0, st, returns, value_preds, rows, N, partial);
-    if (final)
-        hipLaunchKernelGGL(fa_adv_onepass_final_kernel, dim3(1), dim3(64 * N), 0, st, partial, nblocks, N, returns, value_preds,
-                           (double)rows, moments_out, mean_out, std_out);
+        hipLaunchKernelGGL(fa_adv_onepass_kernel, dim3(nblocks), dim3(256), 0, st, a.returns, a.value_preds, rows, a.N,
+                           partial);
     return hipGetLastError();
 }
 
@@ -1134,11 +1096,11 @@ hipError_t fa_launch_adv_stats(int pass, const float *returns, const float *valu
     return hipGetLastError();
 }
 
-hipError_t fa_launch_adv_norm(const float *returns, const float *value_preds, const double *mean,
-                              const double *std_, long long total, int N, float *out, hipStream_t st) {
+hipError_t fa_launch_adv_norm(const FaTailArgs &a, const double *mean, const double *std_, float *out, hipStream_t st) {
+    const long long total = a.total();
     long long want = (total + 255) / 256;
     const int grid = (int)(want < 2048 ? (want < 1 ? 1 : want) : 2048);
-    hipLaunchKernelGGL(fa_adv_norm_kernel, dim3(grid), dim3(256), 0, st, returns, value_preds, mean, std_,
-                       total, N, out);
+    hipLaunchKernelGGL(fa_adv_norm_kernel, dim3(grid), dim3(256), 0, st, a.returns, a.value_preds, mean, std_,
+                       total, a.N, out);
     return hipGetLastError();
 }

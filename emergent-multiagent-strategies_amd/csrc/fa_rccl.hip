@@ -31,9 +31,9 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include <mutex>
 #include <string>
 
+#include "fa_collect.h"
 #include "fortattack.h"
 
-hipError_t fa_launch_adv_merge(const double *gathered, int W, int N, double *mean_out, double *std_out, hipStream_t st);
 int fa_api_fail(int code, const std::string &msg); // fa_api.hip: sets the thread-local message
 
 namespace {

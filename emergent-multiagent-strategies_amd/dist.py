@@ -154,20 +154,26 @@ def two_pass_mean_std(pass0, pass1, group=None):
     return mean, std, n
 
 
+def _gather_merge(eng, moments, group):
+    """ONE all-gather of this rank's (N,3) moments into the engine's (world, N, 3) buffer (made once per world size),
+    then the exact merge kernel (fa_adv_merge)."""
+    world = dist.get_world_size(group)
+    buf = getattr(eng, "_adv_gather", None)
+    if buf is None or buf.shape[0] != world:
+        buf = eng._adv_gather = torch.zeros((world, eng.N, 3), dtype=torch.float64, device=eng.device)
+    dist.all_gather_into_tensor(buf.view(-1), moments.view(-1), group=group)   # flat: backend-neutral
+    return eng.adv_merge(buf)
+
+
 def adv_mean_std(eng, group=None):
     """Global per-agent advantage mean / unbiased std for the storage bound to `eng`.
     One rank: fa_adv_mean_std (four launches, no collective).  Several ranks: local two-pass
     moments, ONE all-gather of (N,3) doubles per rank, exact merge kernel (fa_adv_merge)."""
     if not exchanging(group):
         return eng.adv_mean_std()
-    world = dist.get_world_size(group)
-    buf = getattr(eng, "_adv_gather", None)
-    if buf is None or buf.shape[0] != world:
-        buf = eng._adv_gather = torch.zeros((world, eng.N, 3), dtype=torch.float64, device=eng.device)
+    if getattr(eng, "_adv_local", None) is None:
         eng._adv_local = torch.zeros((eng.N, 3), dtype=torch.float64, device=eng.device)
-    eng.adv_moments(out=eng._adv_local)
-    dist.all_gather_into_tensor(buf.view(-1), eng._adv_local.view(-1), group=group)   # flat: backend-neutral
-    return eng.adv_merge(buf)
+    return _gather_merge(eng, eng.adv_moments(out=eng._adv_local), group)
 
 
 def gae_adv_mean_std(eng, gamma=0.99, tau=0.95, group=None, exchange=None):
@@ -180,12 +186,7 @@ def gae_adv_mean_std(eng, gamma=0.99, tau=0.95, group=None, exchange=None):
         return exchange.adv_mean_std(eng, mom)
     if not exchanging(group):
         return mean, std
-    world = dist.get_world_size(group)
-    buf = getattr(eng, "_adv_gather", None)
-    if buf is None or buf.shape[0] != world:
-        buf = eng._adv_gather = torch.zeros((world, eng.N, 3), dtype=torch.float64, device=eng.device)
-    dist.all_gather_into_tensor(buf.view(-1), mom.view(-1), group=group)
-    return eng.adv_merge(buf)
+    return _gather_merge(eng, mom, group)
 
 
 def merge_moments(gathered):

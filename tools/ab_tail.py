@@ -1,6 +1,6 @@
 """Experiment (run ON THE GPU BOX): the collector tail of the headline workload (3v3 x 4096 x 128) by form, microseconds
 per call from hipEvents over back-to-back calls, alone and behind the fused rollout launch:
-  old      fa_gae + fa_adv_moments_onepass + fa_adv_normalize   (five launches; FA_GAE_MOMENTS_SEPARATE=1)
+  old      fa_gae + fa_adv_moments_onepass + fa_adv_normalize   (five launches: the separate kernels, called one by one)
   moments  fa_gae_moments                                       (scan with moment partials + fold)
   fused    fa_gae_normalize                                     (scan with moment partials, fold + normalisation)
 usage: ab_tail.py [E] [iters] [team size: 3 = 3v3, 5 = 5v5]"""
@@ -37,7 +37,7 @@ def one(E, iters, G=3, A=3):
 
     forms = {"gae_only": lambda: eng.gae(0.99, 0.95), "old": old, "moments": lambda: eng.gae_moments(0.99, 0.95),
              "fused": lambda: eng.gae_normalize(0.99, 0.95, out=adv)}
-    out = {"lib": os.environ.get("FA_AB_LIB", "product"), "separate": os.environ.get("FA_GAE_MOMENTS_SEPARATE", "0"), "E": E, "team": G}
+    out = {"lib": os.environ.get("FA_AB_LIB", "product"), "E": E, "team": G}
     for name, fn in forms.items():
         for with_rollout in (False, True):
             def call():
@@ -64,6 +64,5 @@ if __name__ == "__main__":
         E = sys.argv[1] if len(sys.argv) > 1 else "4096"
         iters = sys.argv[2] if len(sys.argv) > 2 else "300"
         team = sys.argv[3] if len(sys.argv) > 3 else "3"
-        for sep in ("0", "1"):
-            env = dict(os.environ, FA_AB_TAIL_CHILD="1", FA_GAE_MOMENTS_SEPARATE=sep)
-            subprocess.run([sys.executable, os.path.abspath(__file__), E, iters, team], env=env, check=False)
+        env = dict(os.environ, FA_AB_TAIL_CHILD="1")
+        subprocess.run([sys.executable, os.path.abspath(__file__), E, iters, team], env=env, check=False)
