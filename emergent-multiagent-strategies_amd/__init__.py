@@ -19,3 +19,5 @@ __all__ = ["BatchedFortAttack", "FortAttackGlobalEnv", "make_fortattack_env", "J
 from . import render  # noqa: F401
 from . import record  # noqa: F401
 from .record import EpisodeRecorder, split_episodes  # noqa: F401
+from . import behaviour  # noqa: F401
+from .behaviour import BehaviourMaps, behaviour_chunk_numpy, fingerprint_rows, merge_counts, write_heatmaps  # noqa: F401

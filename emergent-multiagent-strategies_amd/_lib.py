@@ -115,6 +115,10 @@ EXPORTS = {
     "fa_match_latch": (C.c_int, [c_p, c_p]),
     "fa_match_table": (C.c_int, [c_p, c_p, C.POINTER(C.c_int32), c_p]),
     "fa_render": (C.c_int, [c_p, C.POINTER(RenderIO), c_p]),
+    "fa_behaviour_cell_words": (C.c_int64, [c_p]),
+    "fa_behaviour_begin": (C.c_int, [c_p, c_p, C.c_int32, C.c_int32, c_p, c_p]),
+    "fa_behaviour_chunk": (C.c_int, [c_p, c_p]),
+    "fa_behaviour_state": (C.c_int, [c_p, c_p, c_p]),
     "fa_policy_weight_floats": (C.c_int64, []),
     "fa_policy_plain_floats": (C.c_int64, []),
     "fa_attend_forward": (C.c_int, [c_p, c_p, c_p, c_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_p]),

@@ -11,7 +11,7 @@ LIB = os.path.join(CSRC, "libfortattack_hip.so")
 if os.environ.get("FA_LIBRARY"):
     LIB = os.path.abspath(os.environ["FA_LIBRARY"])
 OBJ = os.path.join(CSRC, "_obj")            # objects + assembly of the last build (git-ignored)
-SOURCES = ["fa_step_pipe.hip", "fa_step_classic.hip", "fa_collect.hip", "fa_policy.hip", "fa_match.hip", "fa_render.hip", "fa_attend.hip", "fa_train.hip", "fa_train_dw.hip", "fa_fold.hip", "fa_rccl.hip", "fa_api.hip"]
+SOURCES = ["fa_step_pipe.hip", "fa_step_classic.hip", "fa_collect.hip", "fa_policy.hip", "fa_match.hip", "fa_render.hip", "fa_behaviour.hip", "fa_attend.hip", "fa_train.hip", "fa_train_dw.hip", "fa_fold.hip", "fa_rccl.hip", "fa_api.hip"]
 # -ffp-contract=off: the fp64 step must evaluate every operation as the reference does
 # (no fused multiply-add); no -ffast-math for the same reason.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
@@ -26,7 +26,7 @@ def needs_build():
         return False
     if not os.path.isfile(LIB):
         return True
-    deps = [os.path.join(CSRC, f) for f in SOURCES + ["fa_device.h", "fa_step_common.h", "experiments/fa_step_experiments.h", "fa_probe.h", "fa_policy.h", "fa_match.h", "fa_render.h", "fa_mfma.h", "fa_train.h", "fa_collect.h"]]
+    deps = [os.path.join(CSRC, f) for f in SOURCES + ["fa_device.h", "fa_step_common.h", "experiments/fa_step_experiments.h", "fa_probe.h", "fa_policy.h", "fa_match.h", "fa_render.h", "fa_behaviour.h", "fa_mfma.h", "fa_train.h", "fa_collect.h"]]
     deps.append(os.path.join(ROOT, "include", "fortattack.h"))
     return any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps)
 

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import mpnn_pack
+from .behaviour import BehaviourMaps, fingerprint_rows
 from .learner import _capture_mode
 from .mpnn import MPNN
 from .storage import JointRolloutStorage
@@ -74,10 +75,13 @@ class CrossPlay(object):
     ranks to merge them).  Sampling (deterministic=False) is the reference's evaluation mode: Learner.act samples.
     recorder: a record.EpisodeRecorder over some of the handle's envs (record_envs() picks them; it may also be assigned to
     `.recorder` before begin()): every step's frames are drawn on the device -- inside the chunk's graph when use_graph is
-    set -- and brought to the host once per chunk.  What is played does not depend on it."""
+    set -- and brought to the host once per chunk.  What is played does not depend on it.
+    behaviour: keep the behaviour record of every match-up (behaviour.BehaviourMaps) over the episodes that count for the
+    match: one more launch at the end of every chunk -- the last node of the chunk's graph -- over the storage the chunk
+    left; behaviour_counts() / fingerprints() return it.  What is played, raw() and the storage do not depend on it."""
 
     def __init__(self, eng, guard_policies, attacker_policies, episodes_per_env, num_steps=None, deterministic=False,
-                 sample_seed=0, use_graph=False, recorder=None):
+                 sample_seed=0, use_graph=False, recorder=None, behaviour=False):
         self.eng, self.device = eng, eng.device
         self.E, self.G, self.A, self.N = eng.E, eng.G, eng.A, eng.N
         if not eng.cfg.track_counters:
@@ -107,6 +111,7 @@ class CrossPlay(object):
         self.on_chunk = None        # optional callable(self) after every chunk, before after_update (the storage is whole)
         self.recorder = recorder
         self._attn_out = None       # the step's attention maps, exported only for a recorder that draws them
+        self.behaviour = BehaviourMaps(eng, self.cell, self.n_cells, self.episodes_per_env) if behaviour else None
 
     def record_envs(self, per_cell=1):
         """The first `per_cell` env indices of every match-up cell, in cell order (a cell with fewer envs gives what it has):
@@ -141,8 +146,8 @@ class CrossPlay(object):
         self.storage.obs[:2] = torch.from_numpy(obs.astype(np.float32)).to(self.device)
 
     def _capture(self):
-        """ONE hipGraph for a chunk: T x (act with both pools, env step, latch[, the recorder's frames]).  Every launch argument
-        is a fixed pointer."""
+        """ONE hipGraph for a chunk: T x (act with both pools, env step, latch[, the recorder's frames])[, the behaviour pass].
+        Every launch argument is a fixed pointer."""
         if self.eng.max_time_steps < 8:
             raise ValueError("use_graph needs max_time_steps >= 8 (the warm-up step must not end an episode)")
         self._warm_state()
@@ -150,12 +155,16 @@ class CrossPlay(object):
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             self._step(0)               # code objects loaded before the capture
+            if self.behaviour is not None:
+                self.behaviour.chunk()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, capture_error_mode=_capture_mode()):
             for s in range(self.T):
                 self._step(s)
+            if self.behaviour is not None:
+                self.behaviour.chunk()
         # the warm-up step set prevDist; it survives resets in the reference, so put back "None"
         self.eng.set_state(dict(prev_dist=np.full((self.E, self.N), np.nan)))
         return g
@@ -170,22 +179,28 @@ class CrossPlay(object):
             self._attn_out = self.eng.new_attn_out()        # fixed buffers, allocated before any capture
         self.eng.match_begin(self.cell, self.n_cells, self.episodes_per_env)
         if self.use_graph and self._graph is None:
+            if self.behaviour is not None:
+                self.behaviour.begin()                      # the warm-up launch needs a record; begun again below
             self._graph = self._capture()
             self.eng.match_begin(self.cell, self.n_cells, self.episodes_per_env)   # the warm-up step is no part of the match
         self.eng.collect_reset()
+        if self.behaviour is not None:
+            self.behaviour.begin()                          # after the reset: ep_t starts from the world's time_step
         if rec is not None:
             rec.capture_reset()
         self.steps_run, self.remaining = 0, self.E
 
     def run_chunk(self):
-        """num_steps x (collect_act with both pools -> collect_step(auto_reset) -> match_latch); returns `remaining`, the
-        number of envs still short of their quota (read once, here)."""
+        """num_steps x (collect_act with both pools -> collect_step(auto_reset) -> match_latch)[, the behaviour pass];
+        returns `remaining`, the number of envs still short of their quota (read once, here)."""
         self._counter.add_(1)
         if self._graph is not None:
             self._graph.replay()
         else:
             for s in range(self.T):
                 self._step(s)
+            if self.behaviour is not None:
+                self.behaviour.chunk()
         self.steps_run += self.T
         _, self.remaining = self.eng.match_table(self._raw)
         return self.remaining
@@ -217,3 +232,14 @@ class CrossPlay(object):
     def table(self):
         """(n_guard, n_attacker, 8): the reference's row for every match-up (crossplay_rows)."""
         return crossplay_rows(self.raw().cpu().numpy(), self.G).reshape(self.n_guard, self.n_attacker, 8)
+
+    def behaviour_counts(self):
+        """The behaviour record (behaviour.BehaviourMaps.counts()): a dict of int64 arrays with a leading n_cells axis."""
+        if self.behaviour is None:
+            raise ValueError("CrossPlay: created without behaviour=True")
+        return self.behaviour.counts()
+
+    def fingerprints(self):
+        """(n_guard, n_attacker, len(behaviour.FINGERPRINT_COLUMNS)): behaviour.fingerprint_rows of every match-up."""
+        rows = fingerprint_rows(self.behaviour_counts(), self.eng.cfg.world)
+        return rows.reshape(self.n_guard, self.n_attacker, rows.shape[1])

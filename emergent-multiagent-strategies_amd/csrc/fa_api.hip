@@ -13,6 +13,7 @@
 #include "fa_policy.h"
 #include "fa_match.h"
 #include "fa_render.h"
+#include "fa_behaviour.h"
 #include "fa_train.h"
 #include "fortattack.h"
 
@@ -59,6 +60,8 @@ struct fa_env {
     int grp_tiles_max;
     // match bookkeeping (fa_match.hip): baseline + latched counters per env, see fa_match_begin
     FaMatch match;
+    // behaviour maps (fa_behaviour.hip): per-env episode counters + the launch plan of fa_behaviour_begin
+    FaBehaviour beh;
 };
 
 namespace {
@@ -317,6 +320,10 @@ int fa_create(const fa_config *cfg, fa_env **out) {
     const size_t o_mrw = carve(match_ok ? 2 * EN * sizeof(double) : 0);
     const size_t o_mce = carve(match_ok ? 2 * E * sizeof(int32_t) : 0);
     const size_t o_msc = carve(2 * sizeof(int32_t));
+    // behaviour maps: ep_count, ep_t, the env list (E each) and the slice table
+    const int beh_slices = fa_behaviour_max_slices(cfg->num_envs);
+    const size_t o_beh = carve(3 * E * sizeof(int32_t));
+    const size_t o_bsl = carve((size_t)beh_slices * 4 * sizeof(int32_t));
     env->slab_bytes = off;
     hipError_t he = hipMalloc(&env->slab, env->slab_bytes);
     if (he != hipSuccess) {
@@ -362,6 +369,11 @@ int fa_create(const fa_config *cfg, fa_env **out) {
         m.remaining = reinterpret_cast<int32_t *>(b + o_msc);
         m.overrun = m.remaining + 1;
     }
+    env->beh.ep_count = reinterpret_cast<int32_t *>(b + o_beh);
+    env->beh.ep_t = env->beh.ep_count + E;
+    env->beh.env_list = env->beh.ep_t + E;
+    env->beh.slices = reinterpret_cast<int32_t *>(b + o_bsl);
+    env->beh.max_slices = beh_slices;
 
     // construction state (core.py:102-104): alive, prevDist None (NaN); positions are
     // defined by the first reset.
@@ -742,6 +754,103 @@ int fa_match_table(fa_env *env, double *raw, int32_t *remaining_out, void *strea
     if (flags[1])
         return fail(FA_ERR_STATE, "fa_match_table: an env played beyond episodes_per_env before it was latched "
                                   "(fa_match_latch must follow every one-step launch)");
+    return FA_OK;
+}
+
+// ---- behaviour maps (fa_behaviour.hip) ------------------------------------------------------------------
+int64_t fa_behaviour_cell_words(const fa_env *env) {
+    if (!env) return fail(FA_ERR_INVALID, "fa_behaviour_cell_words: null env");
+    return FA_BEHAVIOUR_CELL_WORDS((int64_t)env->cfg.max_time_steps);
+}
+
+int fa_behaviour_begin(fa_env *env, const int32_t *env_cell, int32_t n_cells, int32_t episodes_per_env, uint64_t *counts,
+                       void *stream) {
+    if (!env || !env_cell || !counts) return fail(FA_ERR_INVALID, "fa_behaviour_begin: null argument");
+    if (n_cells < 1 || n_cells > FA_BEH_MAX_CELLS) return fail(FA_ERR_INVALID, "fa_behaviour_begin: n_cells must be 1..4096");
+    if (episodes_per_env < 0) return fail(FA_ERR_INVALID, "fa_behaviour_begin: episodes_per_env must be >= 0 (0 = no quota)");
+    if (env->cfg.max_time_steps > FA_BEH_MAX_MT)
+        return fail(FA_ERR_INVALID, "fa_behaviour_begin: max_time_steps must be <= 1024 (a cell's record is kept in LDS)");
+    DeviceGuard guard(env->cfg.device_id);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    FaBehaviour &bh = env->beh;
+    const int E = env->cfg.num_envs;
+    bh.begun = 0;
+    // the launch plan: the envs grouped by cell (counting sort, ascending inside a cell; the envs of no cell last), cut into
+    // slices of at most FA_BEH_SLICE envs of one cell
+    std::vector<int32_t> cell(E), list(E), slices;
+    FA_HIP(hipMemcpyAsync(cell.data(), env_cell, (size_t)E * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    FA_HIP(hipStreamSynchronize(s));
+    std::vector<int32_t> start(n_cells + 2, 0);
+    auto group = [&](int32_t c) { return (c >= 0 && c < n_cells) ? c : n_cells; };
+    for (int e = 0; e < E; ++e) ++start[group(cell[e]) + 1];
+    for (int c = 0; c <= n_cells; ++c) start[c + 1] += start[c];
+    {
+        std::vector<int32_t> at(start.begin(), start.end() - 1);
+        for (int e = 0; e < E; ++e) list[at[group(cell[e])]++] = e;
+    }
+    for (int c = 0; c <= n_cells; ++c)
+        for (int32_t f = start[c]; f < start[c + 1]; f += FA_BEH_SLICE) {
+            const int32_t cnt = start[c + 1] - f < FA_BEH_SLICE ? start[c + 1] - f : FA_BEH_SLICE;
+            const int32_t row[4] = {c < n_cells ? c : -1, f, cnt, 0};
+            slices.insert(slices.end(), row, row + 4);
+        }
+    const int n_slices = (int)(slices.size() / 4);
+    if (n_slices > bh.max_slices) return fail(FA_ERR_STATE, "fa_behaviour_begin: slice table overflow");
+    FA_HIP(hipMemcpyAsync(bh.env_list, list.data(), (size_t)E * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (n_slices)
+        FA_HIP(hipMemcpyAsync(bh.slices, slices.data(), slices.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    FA_HIP(hipMemsetAsync(bh.ep_count, 0, (size_t)E * sizeof(int32_t), s));
+    FA_HIP(hipMemcpyAsync(bh.ep_t, env->s.tstep, (size_t)E * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    FA_HIP(hipMemsetAsync(counts, 0, (size_t)n_cells * FA_BEHAVIOUR_CELL_WORDS((size_t)env->cfg.max_time_steps) * sizeof(uint64_t), s));
+    FA_HIP(hipStreamSynchronize(s)); // the host vectors go out of scope
+    bh.counts = counts;
+    bh.n_cells = n_cells;
+    bh.quota = episodes_per_env;
+    bh.n_slices = n_slices;
+    bh.begun = 1;
+    return FA_OK;
+}
+
+int fa_behaviour_chunk(fa_env *env, void *stream) {
+    if (!env) return fail(FA_ERR_INVALID, "fa_behaviour_chunk: null env");
+    if (!env->bound) return fail(FA_ERR_STATE, "fa_behaviour_chunk: no storage bound");
+    if (!env->beh.begun) return fail(FA_ERR_STATE, "fa_behaviour_chunk: no record begun (fa_behaviour_begin)");
+    if (env->st.num_steps >= (1 << 24)) return fail(FA_ERR_INVALID, "fa_behaviour_chunk: num_steps must be < 2^24");
+    DeviceGuard guard(env->cfg.device_id);
+    const FaBehaviour &bh = env->beh;
+    FaBehaviourArgs a;
+    a.obs = env->st.obs;
+    a.actions = env->st.actions;
+    a.done = env->st.done;
+    a.ep_count = bh.ep_count;
+    a.ep_t = bh.ep_t;
+    a.env_list = bh.env_list;
+    a.slices = bh.slices;
+    a.counts = bh.counts;
+    a.T = env->st.num_steps;
+    a.E = env->cfg.num_envs;
+    a.N = env->N;
+    a.G = env->cfg.num_guards;
+    a.MT = env->cfg.max_time_steps;
+    a.quota = bh.quota;
+    a.words = (int32_t)FA_BEHAVIOUR_CELL_WORDS(env->cfg.max_time_steps);
+    const fa_world_consts &w = env->cfg.world;
+    a.x0 = (float)w.wall_xmin;
+    a.sx = (float)(FA_BEHAVIOUR_BX / (w.wall_xmax - w.wall_xmin));
+    a.y0 = (float)w.wall_ymin;
+    a.sy = (float)(FA_BEHAVIOUR_BY / (w.wall_ymax - w.wall_ymin));
+    if (bh.n_slices) FA_HIP(fa_launch_behaviour(a, bh.n_slices, static_cast<hipStream_t>(stream)));
+    return FA_OK;
+}
+
+int fa_behaviour_state(fa_env *env, int32_t *ep_count_host, int32_t *ep_t_host) {
+    if (!env) return fail(FA_ERR_INVALID, "fa_behaviour_state: null env");
+    if (!env->beh.begun) return fail(FA_ERR_STATE, "fa_behaviour_state: no record begun (fa_behaviour_begin)");
+    DeviceGuard guard(env->cfg.device_id);
+    const size_t bytes = (size_t)env->cfg.num_envs * sizeof(int32_t);
+    FA_HIP(hipDeviceSynchronize());
+    if (ep_count_host) FA_HIP(hipMemcpy(ep_count_host, env->beh.ep_count, bytes, hipMemcpyDeviceToHost));
+    if (ep_t_host) FA_HIP(hipMemcpy(ep_t_host, env->beh.ep_t, bytes, hipMemcpyDeviceToHost));
     return FA_OK;
 }
 

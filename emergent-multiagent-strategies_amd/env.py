@@ -361,6 +361,36 @@ class BatchedFortAttack(object):
         _lib.check(self._lib.fa_match_table(self._h, _ptr(out), C.byref(rem), _stream()), "fa_match_table")
         return out, int(rem.value)
 
+    # -- behaviour maps (csrc/fa_behaviour.hip; behaviour.py) ---------------------------------------
+    def behaviour_cell_words(self):
+        """fa_behaviour_cell_words: uint64 words of one cell's behaviour record on this handle."""
+        n = int(self._lib.fa_behaviour_cell_words(self._h))
+        _lib.check(min(n, 0), "fa_behaviour_cell_words")
+        return n
+
+    def behaviour_begin(self, env_cell, n_cells, episodes_per_env, counts):
+        """fa_behaviour_begin: env_cell (E) int32 device tensor; counts a device int64 tensor of at least n_cells *
+        behaviour_cell_words() elements (uint64 words), zeroed here and written by every behaviour_chunk().  Call it after the
+        reset that starts a match.  Synchronises."""
+        assert env_cell.is_cuda and env_cell.dtype == torch.int32 and env_cell.is_contiguous() and env_cell.numel() == self.E
+        assert counts.is_cuda and counts.dtype == torch.int64 and counts.is_contiguous()
+        if 1 <= int(n_cells) <= 4096:       # (out of range: the library says so)
+            assert counts.numel() >= int(n_cells) * self.behaviour_cell_words()
+        _lib.check(self._lib.fa_behaviour_begin(self._h, _ptr(env_cell), int(n_cells), int(episodes_per_env), _ptr(counts),
+                                                _stream()), "fa_behaviour_begin")
+        self._behaviour_keep = (env_cell, counts)   # keep them alive: the library holds the counts pointer
+
+    def behaviour_chunk(self):
+        """fa_behaviour_chunk: the behaviour pass over the bound storage's num_steps rows; one launch, capturable."""
+        _lib.check(self._lib.fa_behaviour_chunk(self._h, _stream()), "fa_behaviour_chunk")
+
+    def behaviour_state(self):
+        """fa_behaviour_state -> (ep_count, ep_t), numpy int32 (E): the per-env counters of the behaviour pass."""
+        ep_count, ep_t = np.empty(self.E, np.int32), np.empty(self.E, np.int32)
+        _lib.check(self._lib.fa_behaviour_state(self._h, ep_count.ctypes.data_as(C.c_void_p), ep_t.ctypes.data_as(C.c_void_p)),
+                   "fa_behaviour_state")
+        return ep_count, ep_t
+
     # -- frames on the device (csrc/fa_render.hip) ------------------------------------------------
     def render(self, env_index, size=350, actions=None, no_laser=None, attn=None, viz_dead=False, viz_attn=True, out=None):
         """fa_render: frame k = env env_index[k] drawn from the device state -> uint8 (K, size, size, 3) on the device, row 0 at

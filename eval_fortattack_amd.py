@@ -16,6 +16,14 @@ Writes to --out-dir:
                                               --record-per-cell envs of every match-up, --record-size pixels a side, drawn on
                                               the device with the guards' attention (test_fortattack.py --render --record
                                               --video-format gif); .npz (array ep0) with --video-format npz
+  behaviour.npz                               only with --behaviour: the integer behaviour maps of every match-up (steps,
+                                              episodes, len_hist, alive_t, occ, shots, deaths, each with a leading
+                                              guards x attackers axis), summed on the device over the episodes that count
+                                              for the match; `fingerprints` (guards, attackers, columns) and `columns`
+  fingerprints.csv                            only with --behaviour: one row per match-up: guard, attacker, the fingerprint
+                                              columns (behaviour.FINGERPRINT_COLUMNS)
+  behaviour_g<guard>_a<attacker>.png          only with --behaviour: the match-up's occ / shots / deaths maps, guards above
+                                              attackers
 
 Differences from the reference scripts: --num-eval-episodes counts episodes PER ENV (every match-up is played by
 num-processes / (guards x attackers) envs, so it gets that many times as many episodes); --guard-ckpts names the series
@@ -46,6 +54,8 @@ def get_args(argv=None):
     p.add_argument("--record-size", type=int, default=128, help="frame side in pixels")
     p.add_argument("--record-per-cell", type=int, default=1, help="envs recorded per match-up")
     p.add_argument("--record-episodes", type=int, default=1, help="episodes recorded per env (<= --num-eval-episodes)")
+    p.add_argument("--behaviour", action="store_true",
+                   help="write the behaviour maps and strategy fingerprints of every match-up (behaviour.npz, fingerprints.csv, PNGs)")
     args = p.parse_args(argv)
     if args.record and not 1 <= args.record_episodes <= args.num_eval_episodes:
         p.error("--record-episodes must be 1 .. --num-eval-episodes (%d)" % args.num_eval_episodes)
@@ -72,7 +82,8 @@ def main():
     E, N, K = args.num_processes, args.num_guards + args.num_attackers, len(attackers)
     eng = fa.BatchedFortAttack(E, args.num_guards, args.num_attackers, args.num_env_steps, base_seed=args.seed)
     cp = fa.CrossPlay(eng, guards, attackers, args.num_eval_episodes, deterministic=args.deterministic,
-                      sample_seed=args.seed + 1, use_graph=not args.no_graph and args.num_env_steps >= 8)
+                      sample_seed=args.seed + 1, use_graph=not args.no_graph and args.num_env_steps >= 8,
+                      behaviour=args.behaviour)
     per_episode = args.num_eval_episodes == 1
     if per_episode:     # each env's one episode return: reward x alive-before (obs[:, 0]), as test_fortattack_v2.py:90
         running = torch.zeros((E, N), dtype=torch.float64, device=eng.device)
@@ -120,6 +131,22 @@ def main():
                     fa.record.write_gif(path, frames)
                 else:
                     fa.record.write_npz(path, [frames])
+    if args.behaviour:
+        counts = cp.behaviour_counts()
+        prints = cp.fingerprints()
+        columns = list(fa.behaviour.FINGERPRINT_COLUMNS)
+        np.savez(os.path.join(out_dir, "behaviour.npz"), fingerprints=prints, columns=np.asarray(columns),
+                 guard_ckpts=np.asarray(args.guard_ckpts), attacker_ckpts=np.asarray(args.attacker_ckpts),
+                 **{k: v.reshape((len(guards), K) + v.shape[1:]) for k, v in counts.items()})
+        with open(os.path.join(out_dir, "fingerprints.csv"), "w") as f:
+            f.write(",".join(["guard", "attacker"] + columns) + "\n")
+            for g, gck in enumerate(args.guard_ckpts):
+                for a, ack in enumerate(args.attacker_ckpts):
+                    f.write(",".join(["%d" % gck, "%d" % ack] + ["%.6g" % v for v in prints[g, a]]) + "\n")
+        for g, gck in enumerate(args.guard_ckpts):
+            for a, ack in enumerate(args.attacker_ckpts):
+                fa.behaviour.write_heatmaps(os.path.join(out_dir, "behaviour_g%d_a%d.png" % (gck, ack)),
+                                            {k: v[g * K + a] for k, v in counts.items()})
     np.set_printoptions(suppress=True, precision=4)
     for k, ck in enumerate(args.guard_ckpts):
         print("guard checkpoint %d" % ck)

@@ -372,6 +372,57 @@ typedef struct fa_render_io {
 } fa_render_io;
 int fa_render(fa_env *env, const fa_render_io *io, void *stream);
 
+/* ---- strategy fingerprints: per match-up behaviour maps -------------------------------------------------
+ * The match table says who wins; these integer histograms say what the teams do: where the agents of each team stand, fire
+ * and die, how many are alive t steps into an episode, and how long episodes last -- per match-up cell, over the bound
+ * storage of a chunk of T = num_steps rows (obs (T+1,E,N,6), actions (T,E,N), done (T,E)), restricted to the first
+ * episodes_per_env episodes of every env.  There is no counterpart in the reference.  Per env e two counters persist between
+ * chunks: ep_count[e] (episodes finished since begin) and ep_t[e] (steps into the episode in flight).  For s = 0 .. T-1:
+ *     if quota > 0 and ep_count[e] >= quota: stop
+ *     t = min(ep_t[e], max_time_steps - 1);  team = 0 for guards, 1 for attackers
+ *     for every agent i with obs[s,e,i,0] != 0:
+ *         occ[c][team][by][bx] += 1;  alive_t[c][team][t] += 1
+ *         if actions[s,e,i] == 7:                    shots[c][team][by][bx] += 1
+ *         if !done[s,e] and obs[s+1,e,i,0] == 0:     deaths[c][team][by][bx] += 1
+ *     steps[c] += 1
+ *     if done[s,e]: len_hist[c][t] += 1; episodes[c] += 1; ep_count[e] += 1; ep_t[e] = 0   else: ep_t[e] += 1
+ * Bins: FA_BEHAVIOUR_BX x FA_BEHAVIOUR_BY over [wall_xmin, wall_xmax] x [wall_ymin, wall_ymax]; with x0 = (float)wall_xmin and
+ * sx = (float)(BX / (wall_xmax - wall_xmin)) (the quotient in double), bx = clamp(floorf((x - x0) * sx), 0, BX-1) -- two
+ * separately rounded float32 operations, clamped in float -- and by likewise, by = 0 at wall_ymin.
+ * Known limit: with auto-reset the terminal state of an episode never reaches the storage, so a death on the step that ends
+ * an episode is not in `deaths` (alive_at_end of the match table covers it).
+ * An env whose cell is outside [0, n_cells) is scanned (its counters advance) and counted nowhere.  All counts are uint64
+ * sums of ones: independent of the order of additions, bitwise reproducible, and shards or ranks merge by plain addition.
+ *
+ * One cell's record is FA_BEHAVIOUR_CELL_WORDS(MT) uint64 words, MT = max_time_steps, in this order: */
+#define FA_BEHAVIOUR_BX 40
+#define FA_BEHAVIOUR_BY 32
+#define FA_BEHAVIOUR_OFF_STEPS 0                                 /* steps                */
+#define FA_BEHAVIOUR_OFF_EPISODES 1                              /* episodes             */
+#define FA_BEHAVIOUR_OFF_LEN_HIST 2                              /* len_hist[MT]         */
+#define FA_BEHAVIOUR_OFF_ALIVE_T(MT) (2 + (MT))                  /* alive_t[2][MT]       */
+#define FA_BEHAVIOUR_OFF_OCC(MT) (2 + 3 * (MT))                  /* occ[2][BY][BX]       */
+#define FA_BEHAVIOUR_OFF_SHOTS(MT) (FA_BEHAVIOUR_OFF_OCC(MT) + 2 * FA_BEHAVIOUR_BY * FA_BEHAVIOUR_BX)    /* shots[2][BY][BX]  */
+#define FA_BEHAVIOUR_OFF_DEATHS(MT) (FA_BEHAVIOUR_OFF_OCC(MT) + 4 * FA_BEHAVIOUR_BY * FA_BEHAVIOUR_BX)   /* deaths[2][BY][BX] */
+#define FA_BEHAVIOUR_CELL_WORDS(MT) (2 + 3 * (MT) + 6 * FA_BEHAVIOUR_BY * FA_BEHAVIOUR_BX)
+/* FA_BEHAVIOUR_CELL_WORDS(max_time_steps) of this handle. */
+int64_t fa_behaviour_cell_words(const fa_env *env);
+/* env_cell: device (E) int32; counts: device, caller owned, n_cells * cell_words uint64, zeroed here.  episodes_per_env = 0:
+ * no quota.  Sets ep_count = 0 and ep_t[e] = the world's time_step[e]: call it AFTER the reset that starts a match, or between
+ * training rollouts.  Builds the per-cell env lists on the host: it synchronises the stream and is never captured.  Does
+ * not need track_counters.  FA_ERR_INVALID: null pointers, n_cells outside 1..4096, episodes_per_env < 0,
+ * max_time_steps > 1024. */
+int fa_behaviour_begin(fa_env *env, const int32_t *env_cell, int32_t n_cells, int32_t episodes_per_env, uint64_t *counts,
+                       void *stream);
+/* The pass above over the bound storage's num_steps rows: ONE launch on fixed pointers, no allocation, no synchronisation
+ * -- it can be captured at the end of a chunk's hipGraph.  The launch follows the plan of the last fa_behaviour_begin: a
+ * captured launch stays valid as long as later begins pass the same env_cell contents, n_cells, episodes_per_env and counts.
+ * FA_ERR_STATE without a bound storage or without a begin. */
+int fa_behaviour_chunk(fa_env *env, void *stream);
+/* The per-env counters as they stand (synchronous; tests / checkpoint): ep_count_host, ep_t_host are HOST (E) int32, either
+ * may be NULL.  FA_ERR_STATE without a begin. */
+int fa_behaviour_state(fa_env *env, int32_t *ep_count_host, int32_t *ep_t_host);
+
 /* number of floats of one team's packed weight buffer; of its leading float32 sections (= a plain-layout buffer) */
 int64_t fa_policy_weight_floats(void);
 int64_t fa_policy_plain_floats(void);
