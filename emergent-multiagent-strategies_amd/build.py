@@ -26,8 +26,9 @@ def needs_build():
         return False
     if not os.path.isfile(LIB):
         return True
-    deps = [os.path.join(CSRC, f) for f in SOURCES + ["fa_device.h", "fa_step_common.h", "experiments/fa_step_experiments.h", "fa_probe.h", "fa_policy.h", "fa_match.h", "fa_render.h", "fa_behaviour.h", "fa_mfma.h", "fa_train.h", "fa_collect.h"]]
-    deps.append(os.path.join(ROOT, "include", "fortattack.h"))
+    import glob
+    deps = [os.path.join(CSRC, f) for f in SOURCES] + [os.path.join(ROOT, "include", "fortattack.h")]
+    deps += glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "experiments", "*.h"))
     return any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps)
 
 

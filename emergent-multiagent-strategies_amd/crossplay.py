@@ -12,7 +12,7 @@ import torch
 
 from . import mpnn_pack
 from .behaviour import BehaviourMaps, fingerprint_rows
-from .learner import _capture_mode
+from .learner import _capture_mode, _warm_state
 from .mpnn import MPNN
 from .storage import JointRolloutStorage
 
@@ -131,26 +131,12 @@ class CrossPlay(object):
         if rec is not None:
             rec.capture(s, self.storage, attn_out)
 
-    def _warm_state(self):
-        """A harmless world for the capture warm-up step (as BatchedLearner._warm_state): teams on opposite walls facing away
-        from each other, so no episode ends and the reset RNG stream is not touched."""
-        E, N, G, A = self.E, self.N, self.G, self.A
-        x = np.concatenate([np.linspace(-0.9, 0.9, G), np.linspace(-0.9, 0.9, A)])
-        y = np.concatenate([np.full(G, 0.6), np.full(A, -0.6)])
-        ang = np.concatenate([np.full(G, np.pi / 2), np.full(A, 3 * np.pi / 2)])
-        tile = lambda v: np.tile(v[None, :], (E, 1))
-        self.eng.set_state(dict(pos_x=tile(x), pos_y=tile(y), vel_x=np.zeros((E, N)), vel_y=np.zeros((E, N)),
-                                ang=tile(ang), prev_dist=np.full((E, N), np.nan),
-                                alive=np.ones((E, N), np.uint8), time_step=np.zeros(E, np.int32)))
-        obs = np.stack([np.ones((E, N)), tile(x), tile(y), tile(ang), np.zeros((E, N)), np.zeros((E, N))], -1)
-        self.storage.obs[:2] = torch.from_numpy(obs.astype(np.float32)).to(self.device)
-
     def _capture(self):
         """ONE hipGraph for a chunk: T x (act with both pools, env step, latch[, the recorder's frames])[, the behaviour pass].
         Every launch argument is a fixed pointer."""
         if self.eng.max_time_steps < 8:
             raise ValueError("use_graph needs max_time_steps >= 8 (the warm-up step must not end an episode)")
-        self._warm_state()
+        _warm_state(self.eng, self.storage, self.G, self.A)
         side = torch.cuda.Stream(self.device)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):

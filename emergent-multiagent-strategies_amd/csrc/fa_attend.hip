@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fa_env.h"
 #include "fa_policy.h"
 
 namespace {
@@ -150,8 +151,8 @@ __global__ __launch_bounds__(256) void fa_attend_kernel(const float *__restrict_
 }
 } // namespace
 
-hipError_t fa_launch_attend(int width, bool backward, const float *g, const float *keys, float *out, float *attn,
-                            const float *dout, float *dg, float *dkeys, int B, int n, int nk, int skip_self, hipStream_t st) {
+static hipError_t fa_launch_attend(int width, bool backward, const float *g, const float *keys, float *out, float *attn,
+                                   const float *dout, float *dg, float *dkeys, int B, int n, int nk, int skip_self, hipStream_t st) {
     const dim3 grid((B + 15) / 16), block(256);
 #define FA_ATT(W_, BW_) hipLaunchKernelGGL((fa_attend_kernel<W_, BW_>), grid, block, 0, st, g, keys, out, attn, dout, dg, dkeys, B, n, nk, skip_self)
     if (width == 128) { if (backward) FA_ATT(128, true); else FA_ATT(128, false); }
@@ -160,3 +161,32 @@ hipError_t fa_launch_attend(int width, bool backward, const float *g, const floa
 #undef FA_ATT
     return hipGetLastError();
 }
+
+static int attend_check(const char *who, int B, int n, int nk, int width) {
+    if (B < 1 || n < 1 || nk < 1 || n > FA_POLICY_MAX_TEAM || nk > FA_POLICY_MAX_TEAM)
+        return fail(FA_ERR_INVALID, std::string(who) + ": need B >= 1 and 1 <= n, nk <= 8");
+    if (width != 64 && width != 128) return fail(FA_ERR_INVALID, std::string(who) + ": width must be 64 or 128");
+    return FA_OK;
+}
+
+extern "C" {
+
+int fa_attend_forward(const float *g, const float *keys, float *out, float *attn, int32_t B, int32_t n, int32_t nk,
+                      int32_t width, int32_t skip_self, void *stream) {
+    if (!g || !keys || !out || !attn) return fail(FA_ERR_INVALID, "fa_attend_forward: null argument");
+    if (int rc = attend_check("fa_attend_forward", B, n, nk, width)) return rc;
+    FA_HIP(fa_launch_attend(width, false, g, keys, out, attn, nullptr, nullptr, nullptr, B, n, nk, skip_self,
+                            static_cast<hipStream_t>(stream)));
+    return FA_OK;
+}
+
+int fa_attend_backward(const float *g, const float *keys, const float *attn, const float *dout, float *dg, float *dkeys,
+                       int32_t B, int32_t n, int32_t nk, int32_t width, int32_t skip_self, void *stream) {
+    if (!g || !keys || !attn || !dout || !dg || !dkeys) return fail(FA_ERR_INVALID, "fa_attend_backward: null argument");
+    if (int rc = attend_check("fa_attend_backward", B, n, nk, width)) return rc;
+    FA_HIP(fa_launch_attend(width, true, g, keys, nullptr, const_cast<float *>(attn), dout, dg, dkeys, B, n, nk, skip_self,
+                            static_cast<hipStream_t>(stream)));
+    return FA_OK;
+}
+
+} // extern "C"

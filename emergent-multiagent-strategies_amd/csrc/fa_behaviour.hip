@@ -17,10 +17,29 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "fa_behaviour.h"
-#include "fortattack.h"
+#include <vector>
+
+#include "fa_env.h"
+
+#define FA_BEH_THREADS 256
+#define FA_BEH_SLICE 16  // envs of ONE cell per workgroup
+#define FA_BEH_TB 64     // steps per block of the done scan / the sample sweep
+#define FA_BEH_MAX_CELLS 4096
+#define FA_BEH_MAX_MT 1024 // the largest record a workgroup keeps in LDS: (2 + 3 * 1024 + 6 * 32 * 40) * 4 = 43 016 bytes
+
+struct FaBehaviourArgs {
+    const float *obs;       // (T+1, E, N, 6)
+    const int64_t *actions; // (T, E, N)
+    const uint8_t *done;    // (T, E)
+    int32_t *ep_count, *ep_t;
+    const int32_t *env_list, *slices;
+    uint64_t *counts;
+    int32_t T, E, N, G, MT, quota, words;
+    float x0, sx, y0, sy;
+};
 
 namespace {
+
 #define FA_BEH_CUT 0xffffffffu // scan result: the env had played its episodes before this step
 #define FA_BEH_DONE 0x10000u   // scan result: t in the low 16 bits (t < FA_BEH_MAX_MT), this flag where the step ended the episode
 
@@ -131,8 +150,115 @@ __global__ __launch_bounds__(FA_BEH_THREADS) void fa_behaviour_kernel(FaBehaviou
 }
 } // namespace
 
-hipError_t fa_launch_behaviour(const FaBehaviourArgs &a, int n_slices, hipStream_t st) {
+static hipError_t fa_launch_behaviour(const FaBehaviourArgs &a, int n_slices, hipStream_t st) {
     const size_t lds = (size_t)(FA_BEH_TB * FA_BEH_SLICE + FA_BEH_SLICE + a.words) * sizeof(uint32_t);
     hipLaunchKernelGGL(fa_behaviour_kernel, dim3((unsigned)n_slices), dim3(FA_BEH_THREADS), lds, st, a);
     return hipGetLastError();
 }
+
+// ep_count, ep_t, the env list (E each) and the slice table
+void fa_behaviour_regions(fa_env *env, FaSlab &slab) {
+    FaBehaviour &bh = env->beh;
+    const size_t E = (size_t)env->cfg.num_envs;
+    bh.max_slices = (env->cfg.num_envs + FA_BEH_SLICE - 1) / FA_BEH_SLICE + FA_BEH_MAX_CELLS + 1;
+    slab.region(bh.ep_count, E, true);
+    slab.region(bh.ep_t, E, true);
+    slab.region(bh.env_list, E);
+    slab.region(bh.slices, (size_t)bh.max_slices * 4);
+}
+
+extern "C" {
+
+int64_t fa_behaviour_cell_words(const fa_env *env) {
+    if (int rc = fa_enter(env, "fa_behaviour_cell_words", false)) return rc;
+    return FA_BEHAVIOUR_CELL_WORDS((int64_t)env->cfg.max_time_steps);
+}
+
+int fa_behaviour_begin(fa_env *env, const int32_t *env_cell, int32_t n_cells, int32_t episodes_per_env, uint64_t *counts,
+                       void *stream) {
+    FA_ENTER(env, "fa_behaviour_begin", false, env_cell, counts);
+    if (n_cells < 1 || n_cells > FA_BEH_MAX_CELLS) return fail(FA_ERR_INVALID, "fa_behaviour_begin: n_cells must be 1..4096");
+    if (episodes_per_env < 0) return fail(FA_ERR_INVALID, "fa_behaviour_begin: episodes_per_env must be >= 0 (0 = no quota)");
+    if (env->cfg.max_time_steps > FA_BEH_MAX_MT)
+        return fail(FA_ERR_INVALID, "fa_behaviour_begin: max_time_steps must be <= 1024 (a cell's record is kept in LDS)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    FaBehaviour &bh = env->beh;
+    const int E = env->cfg.num_envs;
+    bh.begun = 0;
+    // the launch plan: the envs grouped by cell (counting sort, ascending inside a cell; the envs of no cell last), cut into
+    // slices of at most FA_BEH_SLICE envs of one cell
+    std::vector<int32_t> cell(E), list(E), slices;
+    FA_HIP(hipMemcpyAsync(cell.data(), env_cell, (size_t)E * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    FA_HIP(hipStreamSynchronize(s));
+    std::vector<int32_t> start(n_cells + 2, 0);
+    auto group = [&](int32_t c) { return (c >= 0 && c < n_cells) ? c : n_cells; };
+    for (int e = 0; e < E; ++e) ++start[group(cell[e]) + 1];
+    for (int c = 0; c <= n_cells; ++c) start[c + 1] += start[c];
+    {
+        std::vector<int32_t> at(start.begin(), start.end() - 1);
+        for (int e = 0; e < E; ++e) list[at[group(cell[e])]++] = e;
+    }
+    for (int c = 0; c <= n_cells; ++c)
+        for (int32_t f = start[c]; f < start[c + 1]; f += FA_BEH_SLICE) {
+            const int32_t cnt = start[c + 1] - f < FA_BEH_SLICE ? start[c + 1] - f : FA_BEH_SLICE;
+            const int32_t row[4] = {c < n_cells ? c : -1, f, cnt, 0};
+            slices.insert(slices.end(), row, row + 4);
+        }
+    const int n_slices = (int)(slices.size() / 4);
+    if (n_slices > bh.max_slices) return fail(FA_ERR_STATE, "fa_behaviour_begin: slice table overflow");
+    FA_HIP(hipMemcpyAsync(bh.env_list, list.data(), (size_t)E * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (n_slices)
+        FA_HIP(hipMemcpyAsync(bh.slices, slices.data(), slices.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    FA_HIP(hipMemsetAsync(bh.ep_count, 0, (size_t)E * sizeof(int32_t), s));
+    FA_HIP(hipMemcpyAsync(bh.ep_t, env->s.tstep, (size_t)E * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    FA_HIP(hipMemsetAsync(counts, 0, (size_t)n_cells * FA_BEHAVIOUR_CELL_WORDS((size_t)env->cfg.max_time_steps) * sizeof(uint64_t), s));
+    FA_HIP(hipStreamSynchronize(s)); // the host vectors go out of scope
+    bh.counts = counts;
+    bh.n_cells = n_cells;
+    bh.quota = episodes_per_env;
+    bh.n_slices = n_slices;
+    bh.begun = 1;
+    return FA_OK;
+}
+
+int fa_behaviour_chunk(fa_env *env, void *stream) {
+    FA_ENTER(env, "fa_behaviour_chunk", true);
+    if (!env->beh.begun) return fail(FA_ERR_STATE, "fa_behaviour_chunk: no record begun (fa_behaviour_begin)");
+    if (env->st.num_steps >= (1 << 24)) return fail(FA_ERR_INVALID, "fa_behaviour_chunk: num_steps must be < 2^24");
+    const FaBehaviour &bh = env->beh;
+    FaBehaviourArgs a;
+    a.obs = env->st.obs;
+    a.actions = env->st.actions;
+    a.done = env->st.done;
+    a.ep_count = bh.ep_count;
+    a.ep_t = bh.ep_t;
+    a.env_list = bh.env_list;
+    a.slices = bh.slices;
+    a.counts = bh.counts;
+    a.T = env->st.num_steps;
+    a.E = env->cfg.num_envs;
+    a.N = env->N;
+    a.G = env->cfg.num_guards;
+    a.MT = env->cfg.max_time_steps;
+    a.quota = bh.quota;
+    a.words = (int32_t)FA_BEHAVIOUR_CELL_WORDS(env->cfg.max_time_steps);
+    const fa_world_consts &w = env->cfg.world;
+    a.x0 = (float)w.wall_xmin;
+    a.sx = (float)(FA_BEHAVIOUR_BX / (w.wall_xmax - w.wall_xmin));
+    a.y0 = (float)w.wall_ymin;
+    a.sy = (float)(FA_BEHAVIOUR_BY / (w.wall_ymax - w.wall_ymin));
+    if (bh.n_slices) FA_HIP(fa_launch_behaviour(a, bh.n_slices, static_cast<hipStream_t>(stream)));
+    return FA_OK;
+}
+
+int fa_behaviour_state(fa_env *env, int32_t *ep_count_host, int32_t *ep_t_host) {
+    FA_ENTER(env, "fa_behaviour_state", false);
+    if (!env->beh.begun) return fail(FA_ERR_STATE, "fa_behaviour_state: no record begun (fa_behaviour_begin)");
+    const size_t bytes = (size_t)env->cfg.num_envs * sizeof(int32_t);
+    FA_HIP(hipDeviceSynchronize());
+    if (ep_count_host) FA_HIP(hipMemcpy(ep_count_host, env->beh.ep_count, bytes, hipMemcpyDeviceToHost));
+    if (ep_t_host) FA_HIP(hipMemcpy(ep_t_host, env->beh.ep_t, bytes, hipMemcpyDeviceToHost));
+    return FA_OK;
+}
+
+} // extern "C"

@@ -5,7 +5,7 @@
 // These are HBM-streaming kernels: GAE reads r, V, m (12 B) and writes ret (4 B) per
 // (t, e, i); the statistics read ret, V (8 B).  One lane per column, consecutive lanes
 // on consecutive columns => every row access is a coalesced span.
-#include "fa_device.h"
+#include "fa_env.h"
 #include "fa_collect.h"
 
 // Learner.wrap_horizon (learner.py:191-211) + RolloutStorage.compute_returns
@@ -983,12 +983,33 @@ hipError_t fa_launch_adv_merge(const double *gathered, int W, int N, double *mea
     hipLaunchKernelGGL(fa_adv_merge_kernel, dim3(1), dim3(64), 0, st, gathered, W, N, mean_out, std_out);
     return hipGetLastError();
 }
-hipError_t fa_launch_adv_moments_fix(double *stats, int N, hipStream_t st) {
+static hipError_t fa_launch_adv_moments_fix(double *stats, int N, hipStream_t st) {
     hipLaunchKernelGGL(fa_adv_moments_kernel, dim3(1), dim3(64), 0, st, stats, N);
     return hipGetLastError();
 }
 
-hipError_t fa_launch_gae(const FaTailArgs &a, hipStream_t st) {
+// ---- host side --------------------------------------------------------------------------------------
+// The bound rollout storage as the tail's launchers see it, built once per call from the handle (tail_args below).
+// gamma and gamma * tau are rounded to float32 once (torch scalar * tensor).  The kernels take these as plain parameters.
+struct FaTailArgs {
+    const float *rewards, *value_preds, *masks; // (T, E, N), (T + 1, E, N), (T + 1, E, N)
+    float *returns;                             // (T + 1, E, N)
+    const uint8_t *done;                        // (T, E)
+    int T, E, N;
+    float g32, gt32;
+    long long rows() const { return (long long)T * E; }   // samples per agent
+    long long total() const { return rows() * N; }
+};
+
+// Where fa_gae_mom_final_kernel / fa_gae_mom_norm_kernel take the per-agent statistics from.
+enum FaStatSource {
+    FA_STATS_SCAN_PARTIALS,  // fold of fa_gae_mom_kernel's {S, Q} partials; pivot = the agent's first GAE term of env 0
+    FA_STATS_SWEEP_PARTIALS, // fold of fa_adv_onepass[_vec]_kernel's partials; pivot = the agent's advantage in row 0
+    FA_STATS_GATHERED_RANKS, // rank-order merge of gathered (W, N, 3) {n, mean, M2} triples (fa_gae_mom_norm_kernel only)
+};
+
+// fa_gae_kernel / fa_gae_coop_kernel / fa_gae4_kernel by the number of columns
+static hipError_t fa_launch_gae(const FaTailArgs &a, hipStream_t st) {
     const long long EN = (long long)a.E * a.N;
     // four columns per lane pay off only once there are enough columns to fill the chip with
     // 16-byte lanes; below that the one-column kernel has 4x the waves in flight
@@ -1014,27 +1035,29 @@ hipError_t fa_launch_gae(const FaTailArgs &a, hipStream_t st) {
 // lost there with three per CU: 41 us against 34 for the separate kernels at 5v5 x 4096 and 3v3 x 8192; the role-split
 // kernel was not measured beyond 512.)  At 3v3 x 4096 the fused tail takes 23.7 us against 33.7 for the separate kernels.  `partial`
 // (partial_cap doubles) holds a {S, Q} pair per (workgroup, agent).  Returns the number of workgroups or 0.
-int fa_gae_mom_blocks(int T, int E, int N, long long partial_cap) {
+static int fa_gae_mom_blocks(int T, int E, int N, long long partial_cap) {
     const long long EN = (long long)E * N;
     if (EN > 64LL * 512 || T < 1 || (long long)(T + 1) * EN * 4 >= (1LL << 31)) return 0;
     const long long nb = (EN + 63) / 64;
     if (nb > 64 * FA_GAEM_FOLD || nb * N * 2 > partial_cap) return 0;
     return (int)nb;
 }
-hipError_t fa_launch_gae_mom(const FaTailArgs &a, double *partial, int nblocks, hipStream_t st) {
+static hipError_t fa_launch_gae_mom(const FaTailArgs &a, double *partial, int nblocks, hipStream_t st) {
     hipLaunchKernelGGL(fa_gae_mom_kernel, dim3(nblocks), dim3(FA_GAES_THREADS), 0, st, a.rewards, a.value_preds, a.masks, a.returns,
                        a.done, a.T, a.E, a.N, a.g32, a.gt32, partial);
     return hipGetLastError();
 }
-hipError_t fa_launch_gae_mom_final(const FaTailArgs &a, FaStatSource src, const double *stats, int count, double *moments_out,
-                                   double *mean_out, double *std_out, hipStream_t st) {
+// one workgroup folds `count` workgroups of partials (FA_STATS_SCAN_PARTIALS or FA_STATS_SWEEP_PARTIALS)
+static hipError_t fa_launch_gae_mom_final(const FaTailArgs &a, FaStatSource src, const double *stats, int count, double *moments_out,
+                                          double *mean_out, double *std_out, hipStream_t st) {
     hipLaunchKernelGGL(fa_gae_mom_final_kernel, dim3(1), dim3(64 * a.N), 0, st, stats, count, a.N, a.rewards, a.value_preds, a.masks,
                        a.returns, a.T, (long long)a.E * a.N, a.g32, (double)a.T * (double)a.E, moments_out, mean_out,
                        std_out, src == FA_STATS_SWEEP_PARTIALS ? 1 : 0);
     return hipGetLastError();
 }
-hipError_t fa_launch_gae_mom_norm(const FaTailArgs &a, FaStatSource src, const double *stats, int count, float *out,
-                                  double *moments_out, double *mean_out, double *std_out, hipStream_t st) {
+// statistics (fold of `count` workgroups of partials, or merge of `count` ranks) + normalisation in every workgroup
+static hipError_t fa_launch_gae_mom_norm(const FaTailArgs &a, FaStatSource src, const double *stats, int count, float *out,
+                                         double *moments_out, double *mean_out, double *std_out, hipStream_t st) {
     // a lane takes two 16-byte quads per trip; two workgroups of eight waves per CU (measured at config 2's 38 MB:
     // 128 / 256 / 512 / 1024 workgroups -> 31.6 / 29.7 / 30.0 / 31.6 us for the two launches, 512 the best behind the rollout)
     const long long want = (a.total() / 4 + 1023) / 1024;
@@ -1050,7 +1073,7 @@ hipError_t fa_launch_gae_mom_norm(const FaTailArgs &a, FaStatSource src, const d
 
 // The one-pass sweep: `partial` must hold nblocks * N * 2 doubles.  Its partials go to fa_launch_gae_mom_final or
 // fa_launch_gae_mom_norm with FA_STATS_SWEEP_PARTIALS, whose fold takes at most 64 * FA_GAEM_FOLD workgroups.
-hipError_t fa_launch_adv_onepass(const FaTailArgs &a, double *partial, int nblocks, hipStream_t st) {
+static hipError_t fa_launch_adv_onepass(const FaTailArgs &a, double *partial, int nblocks, hipStream_t st) {
     const long long rows = a.rows();
     const bool vec = (rows % 2 == 0) && ((((uintptr_t)a.returns | (uintptr_t)a.value_preds) & 15) == 0);
     if (nblocks > 64 * FA_GAEM_FOLD) nblocks = 64 * FA_GAEM_FOLD;
@@ -1081,9 +1104,11 @@ static void launch_adv_partial(const float *returns, const float *value_preds, c
                            rows, N, partial);
 }
 
-hipError_t fa_launch_adv_stats(int pass, const float *returns, const float *value_preds, const double *mean,
-                               long long rows, int N, double *partial, int nblocks, double *stats,
-                               double *derived, hipStream_t st) {
+// the two-pass statistics: the reference formulation the one-pass code is tested against, kept apart from it (no FaTailArgs,
+// no shared helpers)
+static hipError_t fa_launch_adv_stats(int pass, const float *returns, const float *value_preds, const double *mean,
+                                      long long rows, int N, double *partial, int nblocks, double *stats,
+                                      double *derived, hipStream_t st) {
     if (pass == 0) {
         launch_adv_partial<0>(returns, value_preds, mean, rows, N, partial, nblocks, st);
         hipLaunchKernelGGL(fa_adv_final_kernel<0>, dim3(1), dim3(64 * N), 0, st, partial, nblocks, N,
@@ -1096,7 +1121,7 @@ hipError_t fa_launch_adv_stats(int pass, const float *returns, const float *valu
     return hipGetLastError();
 }
 
-hipError_t fa_launch_adv_norm(const FaTailArgs &a, const double *mean, const double *std_, float *out, hipStream_t st) {
+static hipError_t fa_launch_adv_norm(const FaTailArgs &a, const double *mean, const double *std_, float *out, hipStream_t st) {
     const long long total = a.total();
     long long want = (total + 255) / 256;
     const int grid = (int)(want < 2048 ? (want < 1 ? 1 : want) : 2048);
@@ -1104,3 +1129,164 @@ hipError_t fa_launch_adv_norm(const FaTailArgs &a, const double *mean, const dou
                        total, a.N, out);
     return hipGetLastError();
 }
+
+// ---- the exports (include/fortattack.h) --------------------------------------------------------------------
+namespace {
+// The bound storage as the launchers above take it; gamma, gamma * tau rounded to float32 once.
+FaTailArgs tail_args(const fa_env *env, double gamma = 0.0, double tau = 0.0) {
+    const fa_storage &st = env->st;
+    FaTailArgs a;
+    a.rewards = st.rewards;
+    a.value_preds = st.value_preds;
+    a.masks = st.masks;
+    a.returns = st.returns;
+    a.done = st.done;
+    a.T = st.num_steps;
+    a.E = env->cfg.num_envs;
+    a.N = env->N;
+    a.g32 = (float)gamma;
+    a.gt32 = (float)(gamma * tau);
+    return a;
+}
+
+// How the tail is launched for the bound storage: the workgroup count of every grid that depends on the shape alone.
+struct FaTailPlan {
+    int fused;   // fa_gae_mom_kernel's workgroups; 0: the shape is beyond the fused scan, the separate kernels serve
+    int sweep;   // fa_adv_onepass[_vec]_kernel
+    int twopass; // fa_adv_partial[_vec]_kernel
+};
+FaTailPlan tail_plan(const fa_env *env, const FaTailArgs &a) {
+    FaTailPlan p;
+    p.fused = fa_gae_mom_blocks(a.T, a.E, a.N, (long long)env->adv_blocks * FA_MAX_AGENTS * 2);
+    // a lane takes 2 rows x 4 per trip: one workgroup per 2048 rows, at most two per CU (512: what the fold takes)
+    long long want = (a.rows() + 2047) / 2048;
+    p.sweep = (int)(want < 512 ? (want < 1 ? 1 : want) : 512);
+    // a row per lane and trip, as many workgroups as adv_partial holds
+    want = (a.rows() + 255) / 256;
+    p.twopass = (int)(want < env->adv_blocks ? want : env->adv_blocks);
+    return p;
+}
+
+// The scan and the {S, Q} partials of the advantage moments in env->adv_partial: the fused scan where it serves, else fa_gae
+// and the one-pass sweep.  Returns where the partials come from and how many workgroups wrote them; the caller folds them
+// (fa_launch_gae_mom_final) or folds and normalises (fa_launch_gae_mom_norm).
+struct FaTailPartials {
+    hipError_t err;
+    FaStatSource src;
+    int count;
+};
+FaTailPartials tail_scan_partials(const fa_env *env, const FaTailArgs &a, hipStream_t s) {
+    const FaTailPlan p = tail_plan(env, a);
+    if (p.fused) return {fa_launch_gae_mom(a, env->adv_partial, p.fused, s), FA_STATS_SCAN_PARTIALS, p.fused};
+    hipError_t e = fa_launch_gae(a, s);
+    if (e == hipSuccess) e = fa_launch_adv_onepass(a, env->adv_partial, p.sweep, s);
+    return {e, FA_STATS_SWEEP_PARTIALS, p.sweep};
+}
+} // namespace
+
+extern "C" {
+
+int fa_gae(fa_env *env, double gamma, double tau, void *stream) {
+    FA_ENTER(env, "fa_gae", true);
+    FA_HIP(fa_launch_gae(tail_args(env, gamma, tau), static_cast<hipStream_t>(stream)));
+    return FA_OK;
+}
+
+int fa_gae_moments(fa_env *env, double gamma, double tau, double *moments_out, double *mean_out, double *std_out,
+                   void *stream) {
+    FA_ENTER(env, "fa_gae_moments", true);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const FaTailArgs a = tail_args(env, gamma, tau);
+    // scan + moment partials (two launches beyond the fused scan), then one workgroup folds them
+    const FaTailPartials p = tail_scan_partials(env, a, s);
+    FA_HIP(p.err);
+    FA_HIP(fa_launch_gae_mom_final(a, p.src, env->adv_partial, p.count, moments_out, mean_out, std_out, s));
+    return FA_OK;
+}
+
+int fa_gae_normalize(fa_env *env, double gamma, double tau, float *adv_out, double *moments_out, double *mean_out,
+                     double *std_out, void *stream) {
+    FA_ENTER(env, "fa_gae_normalize", true, adv_out);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const FaTailArgs a = tail_args(env, gamma, tau);
+    // scan + moment partials; fold + normalisation by every workgroup -- two launches, three beyond the fused scan (instead
+    // of four), nothing dirty left behind the last one
+    const FaTailPartials p = tail_scan_partials(env, a, s);
+    FA_HIP(p.err);
+    FA_HIP(fa_launch_gae_mom_norm(a, p.src, env->adv_partial, p.count, adv_out, moments_out, mean_out, std_out, s));
+    return FA_OK;
+}
+
+int fa_adv_moments_onepass(fa_env *env, double *moments_out, double *mean_out, double *std_out, void *stream) {
+    FA_ENTER(env, "fa_adv_moments_onepass", true);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const FaTailArgs a = tail_args(env);
+    const int nblocks = tail_plan(env, a).sweep;
+    FA_HIP(fa_launch_adv_onepass(a, env->adv_partial, nblocks, s));
+    FA_HIP(fa_launch_gae_mom_final(a, FA_STATS_SWEEP_PARTIALS, env->adv_partial, nblocks, moments_out, mean_out,
+                                   std_out, s));
+    return FA_OK;
+}
+
+int fa_adv_stats(fa_env *env, int32_t pass, const double *mean, double *stats, void *stream) {
+    FA_ENTER(env, "fa_adv_stats", true, stats);
+    if (pass != 0 && pass != 1) return fail(FA_ERR_INVALID, "fa_adv_stats: pass must be 0 or 1");
+    if (pass == 1 && !mean) return fail(FA_ERR_INVALID, "fa_adv_stats: pass 1 needs mean");
+    const FaTailArgs a = tail_args(env);
+    FA_HIP(fa_launch_adv_stats(pass, a.returns, a.value_preds, mean, a.rows(), a.N, env->adv_partial,
+                               tail_plan(env, a).twopass, stats, nullptr, static_cast<hipStream_t>(stream)));
+    return FA_OK;
+}
+
+int fa_adv_mean_std(fa_env *env, double *mean_out, double *std_out, void *stream) {
+    FA_ENTER(env, "fa_adv_mean_std", true, mean_out, std_out);
+    const FaTailArgs a = tail_args(env);
+    const int nblocks = tail_plan(env, a).twopass;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    FA_HIP(fa_launch_adv_stats(0, a.returns, a.value_preds, nullptr, a.rows(), a.N, env->adv_partial, nblocks,
+                               env->adv_stats, mean_out, s));
+    FA_HIP(fa_launch_adv_stats(1, a.returns, a.value_preds, mean_out, a.rows(), a.N, env->adv_partial, nblocks,
+                               env->adv_stats, std_out, s));
+    return FA_OK;
+}
+
+int fa_adv_moments(fa_env *env, double *moments_out, void *stream) {
+    FA_ENTER(env, "fa_adv_moments", true, moments_out);
+    const FaTailArgs a = tail_args(env);
+    const int nblocks = tail_plan(env, a).twopass;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    double *mean = env->adv_stats + 3 * FA_MAX_AGENTS; // scratch: local mean
+    FA_HIP(fa_launch_adv_stats(0, a.returns, a.value_preds, nullptr, a.rows(), a.N, env->adv_partial, nblocks,
+                               moments_out, mean, s));
+    FA_HIP(fa_launch_adv_stats(1, a.returns, a.value_preds, mean, a.rows(), a.N, env->adv_partial, nblocks,
+                               moments_out, nullptr, s));
+    FA_HIP(fa_launch_adv_moments_fix(moments_out, a.N, s));
+    return FA_OK;
+}
+
+int fa_adv_merge(fa_env *env, const double *gathered, int32_t world, double *mean_out, double *std_out,
+                 void *stream) {
+    FA_ENTER(env, "fa_adv_merge", false, gathered, mean_out, std_out);
+    if (world < 1) return fail(FA_ERR_INVALID, "fa_adv_merge: world must be >= 1");
+    FA_HIP(fa_launch_adv_merge(gathered, world, env->N, mean_out, std_out, static_cast<hipStream_t>(stream)));
+    return FA_OK;
+}
+
+int fa_adv_merge_normalize(fa_env *env, const double *gathered, int32_t world, float *adv_out, double *mean_out, double *std_out,
+                           void *stream) {
+    FA_ENTER(env, "fa_adv_merge_normalize", false, gathered, adv_out);
+    if (world < 1) return fail(FA_ERR_INVALID, "fa_adv_merge_normalize: world must be >= 1");
+    // (this export has always looked at `world` before the storage: the storage check keeps its place)
+    if (!env->bound) return fail(FA_ERR_STATE, "fa_adv_merge_normalize: no storage bound");
+    FA_HIP(fa_launch_gae_mom_norm(tail_args(env), FA_STATS_GATHERED_RANKS, gathered, world, adv_out, nullptr, mean_out,
+                                  std_out, static_cast<hipStream_t>(stream)));
+    return FA_OK;
+}
+
+int fa_adv_normalize(fa_env *env, const double *mean, const double *std_, float *adv_out, void *stream) {
+    FA_ENTER(env, "fa_adv_normalize", true, mean, std_, adv_out);
+    FA_HIP(fa_launch_adv_norm(tail_args(env), mean, std_, adv_out, static_cast<hipStream_t>(stream)));
+    return FA_OK;
+}
+
+} // extern "C"

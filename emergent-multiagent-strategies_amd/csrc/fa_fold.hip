@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fa_env.h"
 #include "fa_train.h"
 
 #define FA_TASK_SLICES 64
@@ -105,11 +106,27 @@ __global__ __launch_bounds__(256) void fa_pack_kernel(const float *__restrict__ 
 }
 } // namespace
 
-hipError_t fa_launch_tasks(const fa_task *tasks, int n, hipStream_t st) {
+static hipError_t fa_launch_tasks(const fa_task *tasks, int n, hipStream_t st) {
     if (n > 0) hipLaunchKernelGGL(fa_task_kernel, dim3(n, FA_TASK_SLICES), dim3(256), 0, st, tasks);
     return hipGetLastError();
 }
-hipError_t fa_launch_pack(const float *plain, float *w, float *wt, hipStream_t st) {
+static hipError_t fa_launch_pack(const float *plain, float *w, float *wt, hipStream_t st) {
     hipLaunchKernelGGL(fa_pack_kernel, dim3((FA_POLICY_PLAIN_FLOATS + 255) / 256), dim3(256), 0, st, plain, w, wt);
     return hipGetLastError();
 }
+
+extern "C" {
+
+int fa_run_tasks(const fa_task *tasks, int32_t n, void *stream) {
+    if (!tasks || n < 0) return fail(FA_ERR_INVALID, "fa_run_tasks: null task list");
+    FA_HIP(fa_launch_tasks(tasks, n, static_cast<hipStream_t>(stream)));
+    return FA_OK;
+}
+
+int fa_pack_weights(const float *plain, float *weights, float *weights_t, void *stream) {
+    if (!plain || !weights || !weights_t) return fail(FA_ERR_INVALID, "fa_pack_weights: null argument");
+    FA_HIP(fa_launch_pack(plain, weights, weights_t, static_cast<hipStream_t>(stream)));
+    return FA_OK;
+}
+
+} // extern "C"

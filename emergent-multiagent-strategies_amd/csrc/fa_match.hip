@@ -8,7 +8,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "fa_match.h"
+#include "fa_env.h"
+
+#define FA_MATCH_THREADS 256 // workgroup of the table kernel: one per cell
 
 namespace {
 __device__ __forceinline__ uint32_t episodes_since(const FaState &s, const FaMatch &m, int e) {
@@ -89,18 +91,76 @@ __global__ __launch_bounds__(FA_MATCH_THREADS) void fa_match_table_kernel(FaStat
 }
 } // namespace
 
-hipError_t fa_launch_match_begin(const FaState &s, const FaMatch &m, const int32_t *env_cell, int E, int N, hipStream_t st) {
+static hipError_t fa_launch_match_begin(const FaState &s, const FaMatch &m, const int32_t *env_cell, int E, int N, hipStream_t st) {
     hipLaunchKernelGGL(fa_match_begin_kernel, dim3((E + 255) / 256), dim3(256), 0, st, s, m, env_cell, E, N);
     return hipGetLastError();
 }
 
-hipError_t fa_launch_match_latch(const FaState &s, const FaMatch &m, int E, int N, hipStream_t st) {
+static hipError_t fa_launch_match_latch(const FaState &s, const FaMatch &m, int E, int N, hipStream_t st) {
     hipLaunchKernelGGL(fa_match_latch_kernel, dim3((E + 255) / 256), dim3(256), 0, st, s, m, E, N, (uint32_t)m.episodes_per_env);
     return hipGetLastError();
 }
 
-hipError_t fa_launch_match_table(const FaState &s, const FaMatch &m, int E, int N, double *raw, hipStream_t st) {
+static hipError_t fa_launch_match_table(const FaState &s, const FaMatch &m, int E, int N, double *raw, hipStream_t st) {
     hipLaunchKernelGGL(fa_match_table_kernel, dim3(m.n_cells), dim3(FA_MATCH_THREADS), 0, st, s, m, E, N,
                        (uint32_t)m.episodes_per_env, raw);
     return hipGetLastError();
 }
+
+// baseline and latched copies of the three counters, the per-env cell / latch flag, two scalars; with track_counters = 0 the
+// per-env regions are empty and the handle's pointers stay null (every export below refuses such a handle)
+void fa_match_regions(fa_env *env, FaSlab &slab) {
+    const bool on = env->cfg.track_counters != 0;
+    FaMatch unused;
+    FaMatch &m = on ? env->match : unused;
+    const size_t E = on ? (size_t)env->cfg.num_envs : 0, EN = E * env->N;
+    slab.region(m.base_rc, E * 3, true);
+    slab.region(m.lat_rc, E * 3);
+    slab.region(m.base_alive, EN, true);
+    slab.region(m.lat_alive, EN);
+    slab.region(m.base_rew, EN, true);
+    slab.region(m.lat_rew, EN);
+    slab.region(m.cell, E, true);
+    slab.region(m.latched, E);
+    slab.region(m.remaining, 1, true);
+    slab.region(m.overrun, 1);
+}
+
+extern "C" {
+
+int fa_match_begin(fa_env *env, const int32_t *env_cell, int32_t n_cells, int32_t episodes_per_env, void *stream) {
+    FA_ENTER(env, "fa_match_begin", false, env_cell);
+    if (!env->cfg.track_counters) return fail(FA_ERR_STATE, "fa_match_begin: the handle was created with track_counters = 0");
+    if (n_cells < 1 || episodes_per_env < 1) return fail(FA_ERR_INVALID, "fa_match_begin: need n_cells >= 1 and episodes_per_env >= 1");
+    env->match.n_cells = n_cells;
+    env->match.episodes_per_env = episodes_per_env;
+    env->match.begun = 1;
+    FA_HIP(fa_launch_match_begin(env->s, env->match, env_cell, env->cfg.num_envs, env->N, static_cast<hipStream_t>(stream)));
+    return FA_OK;
+}
+
+int fa_match_latch(fa_env *env, void *stream) {
+    FA_ENTER(env, "fa_match_latch", false);
+    if (!env->cfg.track_counters) return fail(FA_ERR_STATE, "fa_match_latch: the handle was created with track_counters = 0");
+    if (!env->match.begun) return fail(FA_ERR_STATE, "fa_match_latch: no match begun (fa_match_begin)");
+    FA_HIP(fa_launch_match_latch(env->s, env->match, env->cfg.num_envs, env->N, static_cast<hipStream_t>(stream)));
+    return FA_OK;
+}
+
+int fa_match_table(fa_env *env, double *raw, int32_t *remaining_out, void *stream) {
+    FA_ENTER(env, "fa_match_table", false, raw);
+    if (!env->cfg.track_counters) return fail(FA_ERR_STATE, "fa_match_table: the handle was created with track_counters = 0");
+    if (!env->match.begun) return fail(FA_ERR_STATE, "fa_match_table: no match begun (fa_match_begin)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    FA_HIP(fa_launch_match_table(env->s, env->match, env->cfg.num_envs, env->N, raw, s));
+    int32_t flags[2] = {0, 0}; // remaining, overrun: adjacent device scalars
+    FA_HIP(hipMemcpyAsync(flags, env->match.remaining, sizeof(flags), hipMemcpyDeviceToHost, s));
+    FA_HIP(hipStreamSynchronize(s));
+    if (remaining_out) *remaining_out = flags[0];
+    if (flags[1])
+        return fail(FA_ERR_STATE, "fa_match_table: an env played beyond episodes_per_env before it was latched "
+                                  "(fa_match_latch must follow every one-step launch)");
+    return FA_OK;
+}
+
+} // extern "C"

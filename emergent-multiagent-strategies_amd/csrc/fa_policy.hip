@@ -39,8 +39,33 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "fa_env.h"
 #include "fa_policy.h"
 #include "fa_mfma.h"
+
+struct FaPolicyArgs {
+    const float *obs;      // (E, N, 6) observation row
+    const float *w[2];     // packed weights: guards' policy, attackers' policy
+    float *value;          // (E, N) or null
+    int64_t *action;       // (E, N)
+    float *logp;           // (E, N)
+    const int64_t *counter; // device scalar mixed into the sampling stream (bumped once per rollout) or null
+    uint64_t seed;
+    int64_t env_offset;
+    int32_t E, G, A, step, deterministic, value_only;
+    // ensembles of frozen strategies (learner.py:119-140; cross-play: a guard pool too), per team t = blockIdx.y: the team's envs
+    // grouped by ITS strategy.  A team without a pool (env_list[t] null) walks contiguous env ranges with w[t].
+    const float *pool[2];             // the team's packed weight buffers back to back, or null
+    const int32_t *env_list[2];       // [tiles][ET] env index of every tile slot (-1 = empty), from fa_group_envs_kernel
+    const int32_t *tile_strategy[2];  // [tiles] strategy of the tile's envs (-1 = unused tile)
+    int32_t tiles;                    // grid size in tiles when either env_list is set (>= the contiguous tiling's)
+    // the softmax weights of the forward (policy.attn_mat / opp_attn_mat, mpnn.py:139-140, :158-166), float32, row (e, i) of
+    // team t at ((size_t)e * n + i) * nk: team_attn (E, n, n) = the last message-passing round's, opp_attn (E, n, m).
+    // Any non-null entry selects the exporting instantiation; a null entry among them is not written.
+    float *team_attn[2], *opp_attn[2];
+};
+#define FA_POLICY_MAX_POOL 64 // strategies in an ensemble
+
 #define FA_PROBE_POLICY_TU
 #include "fa_probe.h"
 
@@ -490,9 +515,11 @@ static int policy_rows(int E, int G, int A) {
     const int wgs96 = 2 * ((E + et96 - 1) / et96);
     return wgs96 < 192 ? 64 : FA_POLICY_ROWS;
 }
-int fa_policy_tile_envs(int E, int G, int A) { return policy_rows(E, G, A) / (G > A ? G : A); }
+static int fa_policy_tile_envs(int E, int G, int A) { return policy_rows(E, G, A) / (G > A ? G : A); }
 
-hipError_t fa_launch_group_envs(const int32_t *const env_strategy[2], int E, const int pool_size[2], int G, int A,
+// envs -> tiles of equal strategy, one workgroup per pooled team t (env_strategy[t] non-null): env_list[t] / tile_strategy[t] for a
+// launch with pool[t]
+static hipError_t fa_launch_group_envs(const int32_t *const env_strategy[2], int E, const int pool_size[2], int G, int A,
                                 int32_t *const env_list[2], int32_t *const tile_strategy[2], int tiles_max, hipStream_t st) {
     FaGroupArgs g;
     for (int t = 0; t < 2; ++t) {
@@ -505,7 +532,7 @@ hipError_t fa_launch_group_envs(const int32_t *const env_strategy[2], int E, con
     return hipGetLastError();
 }
 
-hipError_t fa_launch_policy(const FaPolicyArgs &a, hipStream_t st) {
+static hipError_t fa_launch_policy(const FaPolicyArgs &a, hipStream_t st) {
     const int ET = fa_policy_tile_envs(a.E, a.G, a.A);
     const int tiles = (a.env_list[0] || a.env_list[1]) ? a.tiles : (a.E + ET - 1) / ET;
     // the exporting instantiation iff any of the four attention matrices is wanted (a null one among them is skipped)
@@ -517,3 +544,107 @@ hipError_t fa_launch_policy(const FaPolicyArgs &a, hipStream_t st) {
     else hipLaunchKernelGGL((fa_policy_kernel<3, FA_POLICY_WAVES, true>), dim3(tiles, 2), dim3(FA_POLICY_WAVES * 64), 0, st, a);
     return hipGetLastError();
 }
+
+// the two teams' grouping lists of a pooled launch (fa_group_envs_kernel), where the fused policy serves the team sizes
+void fa_policy_regions(fa_env *env, FaSlab &slab) {
+    const fa_config &cfg = env->cfg;
+    const bool fused_ok = cfg.num_guards <= FA_POLICY_MAX_TEAM && cfg.num_attackers <= FA_POLICY_MAX_TEAM;
+    // sized for the smallest tile the policy kernel may choose (64 rows), slots counted at the largest (96)
+    const int n_max = cfg.num_guards > cfg.num_attackers ? cfg.num_guards : cfg.num_attackers;
+    const int tile_envs = fused_ok ? 64 / n_max : 1;
+    env->grp_tiles_max = fused_ok ? (cfg.num_envs + tile_envs - 1) / tile_envs + FA_POLICY_MAX_POOL : 0;
+    for (int t = 0; t < 2; ++t) {
+        slab.region(env->grp_env_list[t], (size_t)env->grp_tiles_max * (FA_POLICY_ROWS / n_max + 1));
+        slab.region(env->grp_tile_strategy[t], (size_t)env->grp_tiles_max);
+    }
+}
+
+// One forward of both teams; `io` as the caller passed it (fa_policy_act) or with the bound storage's rows in place of its
+// obs / value / action / log_prob (fa_collect_act).
+static int policy_launch(fa_env *env, const fa_policy_io &io, void *stream, const char *who) {
+    if (!io.obs || (!io.weights[0] && io.guard_pool_size <= 0) || (!io.weights[1] && io.pool_size <= 0))
+        return fail(FA_ERR_INVALID, std::string(who) + ": obs and both teams' weight buffers are required");
+    if (!io.value_only && (!io.action || !io.log_prob)) return fail(FA_ERR_INVALID, std::string(who) + ": action and log_prob are required");
+    if (io.value_only && !io.value) return fail(FA_ERR_INVALID, std::string(who) + ": value_only needs value");
+    if (env->cfg.num_guards > FA_POLICY_MAX_TEAM || env->cfg.num_attackers > FA_POLICY_MAX_TEAM)
+        return fail(FA_ERR_INVALID, std::string(who) + ": teams of more than 8 agents are not supported by the fused policy");
+    if (io.pool_size > 0 && (!io.attacker_pool || !io.env_strategy || io.pool_size > FA_POLICY_MAX_POOL))
+        return fail(FA_ERR_INVALID, std::string(who) + ": an attacker pool needs weights, env_strategy and <= 64 strategies");
+    if (io.guard_pool_size > 0 && (!io.guard_pool || !io.env_guard_strategy || io.guard_pool_size > FA_POLICY_MAX_POOL))
+        return fail(FA_ERR_INVALID, std::string(who) + ": a guard pool needs guard_pool, env_guard_strategy and <= 64 strategies");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    FaPolicyArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.obs = io.obs;
+    a.w[0] = io.weights[0];
+    a.w[1] = io.weights[1];
+    a.value = io.value;
+    a.action = io.action;
+    a.logp = io.log_prob;
+    a.counter = io.counter;
+    a.seed = io.seed;
+    a.env_offset = env->cfg.env_offset;
+    a.E = env->cfg.num_envs;
+    a.G = env->cfg.num_guards;
+    a.A = env->cfg.num_attackers;
+    a.step = io.step;
+    a.deterministic = io.deterministic;
+    a.value_only = io.value_only;
+    for (int t = 0; t < 2; ++t) { // attention export: any non-null pointer selects the exporting kernel
+        a.team_attn[t] = io.team_attn[t];
+        a.opp_attn[t] = io.opp_attn[t];
+    }
+    if (io.pool_size > 0 || io.guard_pool_size > 0) { // group each pooled team's envs into tiles of equal strategy, then one launch
+        const int32_t *const strat[2] = {io.env_guard_strategy, io.env_strategy};
+        const float *const pools[2] = {io.guard_pool, io.attacker_pool};
+        const int sizes[2] = {io.guard_pool_size > 0 ? io.guard_pool_size : 0, io.pool_size > 0 ? io.pool_size : 0};
+        FA_HIP(fa_launch_group_envs(strat, a.E, sizes, a.G, a.A, env->grp_env_list, env->grp_tile_strategy,
+                                    env->grp_tiles_max, s));
+        for (int t = 0; t < 2; ++t) {
+            if (sizes[t] == 0) continue;
+            a.pool[t] = pools[t];
+            a.env_list[t] = env->grp_env_list[t];
+            a.tile_strategy[t] = env->grp_tile_strategy[t];
+        }
+        a.tiles = env->grp_tiles_max;
+    }
+    FA_HIP(fa_launch_policy(a, s));
+    return FA_OK;
+}
+
+extern "C" {
+
+int fa_policy_act(fa_env *env, const fa_policy_io *io, void *stream) {
+    FA_ENTER(env, "fa_policy_act", false, io);
+    return policy_launch(env, *io, stream, "fa_policy_act");
+}
+
+int fa_collect_act(fa_env *env, int32_t step, const fa_policy_io *io, void *stream) {
+    FA_ENTER(env, "fa_collect_act", true, io);
+    const fa_storage &st = env->st;
+    const int value_only = io->value_only;
+    if (step < 0 || step > st.num_steps || (!value_only && step == st.num_steps))
+        return fail(FA_ERR_INVALID, "fa_collect_act: step outside the bound storage");
+    if (!value_only && !st.action_log_probs) return fail(FA_ERR_STATE, "fa_collect_act: storage has no action_log_probs");
+    const size_t EN = (size_t)env->cfg.num_envs * env->N;
+    fa_policy_io row = *io; // the storage's rows of this step
+    row.obs = st.obs + (size_t)step * EN * FA_OBS_DIM;
+    row.value = st.value_preds + (size_t)step * EN;
+    row.action = value_only ? nullptr : st.actions + (size_t)step * EN;
+    row.log_prob = value_only ? nullptr : st.action_log_probs + (size_t)step * EN;
+    row.step = step;
+    return policy_launch(env, row, stream, "fa_collect_act");
+}
+
+const char *fa_policy_variant(fa_env *env) {
+    if (!env) return "";
+    const int E = env->cfg.num_envs, G = env->cfg.num_guards, A = env->cfg.num_attackers;
+    if (G > FA_POLICY_MAX_TEAM || A > FA_POLICY_MAX_TEAM) return "";
+    const int n_max = G > A ? G : A;
+    return fa_policy_tile_envs(E, G, A) * n_max > 64 ? "fa_policy_kernel<3, 8>" : "fa_policy_kernel<2, 4>";
+}
+
+int64_t fa_policy_weight_floats(void) { return FA_POLICY_WEIGHT_FLOATS; }
+int64_t fa_policy_plain_floats(void) { return FA_POLICY_PLAIN_FLOATS; }
+
+} // extern "C"

@@ -32,9 +32,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include <string>
 
 #include "fa_collect.h"
-#include "fortattack.h"
-
-int fa_api_fail(int code, const std::string &msg); // fa_api.hip: sets the thread-local message
+#include "fa_env.h"
 
 namespace {
 struct Rccl {
@@ -91,14 +89,14 @@ Rccl &rccl() {
 int need(const char *who) {
     Rccl &r = rccl();
     if (r.handle) return FA_OK;
-    return fa_api_fail(FA_ERR_STATE, std::string(who) + ": RCCL is not available (" + r.error + ")");
+    return fail(FA_ERR_STATE, std::string(who) + ": RCCL is not available (" + r.error + ")");
 }
 
 #define FA_NCCL(who, expr)                                                                                   \
     do {                                                                                                     \
         ncclResult_t _r = (expr);                                                                            \
         if (_r != ncclSuccess)                                                                               \
-            return fa_api_fail(FA_ERR_HIP, std::string(who) + ": " #expr ": " + rccl().GetErrorString(_r));  \
+            return fail(FA_ERR_HIP, std::string(who) + ": " #expr ": " + rccl().GetErrorString(_r));  \
     } while (0)
 } // namespace
 
@@ -109,7 +107,7 @@ int fa_rccl_available(void) { return rccl().handle ? 1 : 0; }
 const char *fa_rccl_library(void) { return rccl().handle ? rccl().path.c_str() : ""; }
 
 int fa_rccl_unique_id(void *id_out) {
-    if (!id_out) return fa_api_fail(FA_ERR_INVALID, "fa_rccl_unique_id: null argument");
+    if (!id_out) return fail(FA_ERR_INVALID, "fa_rccl_unique_id: null argument");
     if (int rc = need("fa_rccl_unique_id")) return rc;
     static_assert(FA_RCCL_UNIQUE_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "fortattack.h and rccl.h disagree on the id size");
     FA_NCCL("fa_rccl_unique_id", rccl().GetUniqueId(static_cast<ncclUniqueId *>(id_out)));
@@ -117,17 +115,17 @@ int fa_rccl_unique_id(void *id_out) {
 }
 
 int fa_rccl_comm_create(void **comm_out, int32_t nranks, const void *id, int32_t rank, int32_t device_id) {
-    if (!comm_out || !id) return fa_api_fail(FA_ERR_INVALID, "fa_rccl_comm_create: null argument");
-    if (nranks < 1 || rank < 0 || rank >= nranks) return fa_api_fail(FA_ERR_INVALID, "fa_rccl_comm_create: need 0 <= rank < nranks");
+    if (!comm_out || !id) return fail(FA_ERR_INVALID, "fa_rccl_comm_create: null argument");
+    if (nranks < 1 || rank < 0 || rank >= nranks) return fail(FA_ERR_INVALID, "fa_rccl_comm_create: need 0 <= rank < nranks");
     if (int rc = need("fa_rccl_comm_create")) return rc;
     int prev = 0;
     if (hipGetDevice(&prev) != hipSuccess || hipSetDevice(device_id) != hipSuccess)
-        return fa_api_fail(FA_ERR_HIP, "fa_rccl_comm_create: cannot select the device");
+        return fail(FA_ERR_HIP, "fa_rccl_comm_create: cannot select the device");
     ncclUniqueId uid = *static_cast<const ncclUniqueId *>(id);
     ncclComm_t comm = nullptr;
     ncclResult_t r = rccl().CommInitRank(&comm, nranks, uid, rank);
     (void)hipSetDevice(prev);
-    if (r != ncclSuccess) return fa_api_fail(FA_ERR_HIP, std::string("fa_rccl_comm_create: ncclCommInitRank: ") + rccl().GetErrorString(r));
+    if (r != ncclSuccess) return fail(FA_ERR_HIP, std::string("fa_rccl_comm_create: ncclCommInitRank: ") + rccl().GetErrorString(r));
     *comm_out = comm;
     return FA_OK;
 }
@@ -140,7 +138,7 @@ int fa_rccl_comm_destroy(void *comm) {
 }
 
 int fa_rccl_comm_ranks(void *comm) {
-    if (!comm) return fa_api_fail(FA_ERR_INVALID, "fa_rccl_comm_ranks: null communicator");
+    if (!comm) return fail(FA_ERR_INVALID, "fa_rccl_comm_ranks: null communicator");
     if (int rc = need("fa_rccl_comm_ranks")) return rc;
     int n = 0;
     FA_NCCL("fa_rccl_comm_ranks", rccl().CommCount(static_cast<ncclComm_t>(comm), &n));
@@ -150,7 +148,7 @@ int fa_rccl_comm_ranks(void *comm) {
 int fa_adv_allreduce(fa_env *env, const double *moments, double *gathered, void *nccl_comm, double *mean_out,
                      double *std_out, void *stream) {
     if (!env || !moments || !gathered || !nccl_comm || !mean_out || !std_out)
-        return fa_api_fail(FA_ERR_INVALID, "fa_adv_allreduce: null argument");
+        return fail(FA_ERR_INVALID, "fa_adv_allreduce: null argument");
     if (int rc = need("fa_adv_allreduce")) return rc;
     const int N = fa_num_agents(env);
     int world = 0;
@@ -159,14 +157,14 @@ int fa_adv_allreduce(fa_env *env, const double *moments, double *gathered, void 
     // rank r's triple lands at gathered[r]: rank order, so the merge gives every rank the same bits
     FA_NCCL("fa_adv_allreduce", rccl().AllGather(moments, gathered, (size_t)N * 3, ncclFloat64, static_cast<ncclComm_t>(nccl_comm), s));
     if (fa_launch_adv_merge(gathered, world, N, mean_out, std_out, s) != hipSuccess)
-        return fa_api_fail(FA_ERR_HIP, "fa_adv_allreduce: merge kernel launch failed");
+        return fail(FA_ERR_HIP, "fa_adv_allreduce: merge kernel launch failed");
     return FA_OK;
 }
 
 int fa_gae_allreduce_normalize(fa_env *env, double gamma, double tau, void *nccl_comm, double *moments, double *gathered,
                                float *adv_out, double *mean_out, double *std_out, void *stream) {
     if (!env || !moments || !gathered || !nccl_comm || !adv_out || !mean_out || !std_out)
-        return fa_api_fail(FA_ERR_INVALID, "fa_gae_allreduce_normalize: null argument");
+        return fail(FA_ERR_INVALID, "fa_gae_allreduce_normalize: null argument");
     if (int rc = need("fa_gae_allreduce_normalize")) return rc;
     int world = 0;
     FA_NCCL("fa_gae_allreduce_normalize", rccl().CommCount(static_cast<ncclComm_t>(nccl_comm), &world));
@@ -178,7 +176,7 @@ int fa_gae_allreduce_normalize(fa_env *env, double gamma, double tau, void *nccl
 }
 
 int fa_grad_allreduce(float *flat, int64_t n, void *nccl_comm, void *stream) {
-    if (!flat || !nccl_comm || n < 1) return fa_api_fail(FA_ERR_INVALID, "fa_grad_allreduce: null argument");
+    if (!flat || !nccl_comm || n < 1) return fail(FA_ERR_INVALID, "fa_grad_allreduce: null argument");
     if (int rc = need("fa_grad_allreduce")) return rc;
     FA_NCCL("fa_grad_allreduce", rccl().AllReduce(flat, flat, (size_t)n, ncclFloat32, ncclSum, static_cast<ncclComm_t>(nccl_comm),
                                                   static_cast<hipStream_t>(stream)));

@@ -19,8 +19,26 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "fa_render.h"
+#include "fa_env.h"
 #include "fa_step_common.h" // sincos_heading
+
+struct FaRenderArgs {
+    FaState s;
+    const int32_t *env_index; // (K) env of the handle shown by frame k
+    uint8_t *rgb;             // (K, size, size, 3), row 0 = top
+    const int64_t *actions;   // or null; element (e,i) at actions[e*as_e + i*as_i]
+    int64_t as_e, as_i;
+    const uint8_t *no_laser;  // (E) or null
+    const float *team_attn;   // guards' (E,G,G) or null
+    const float *opp_attn;    // guards' (E,G,A) or null
+    int32_t K, size, E, G, A;
+    int32_t viz_dead, attn_on; // attn_on: both maps given and viz_attn set
+    // fortattack.py:368-600 constants, from FaDerived
+    double agent_size, fort_dim, door_x, door_y, wall_xmin, wall_xmax, wall_ymin, wall_ymax, shoot_rad, half_win;
+};
+
+#define FA_RENDER_THREADS 256
+#define FA_RENDER_QUADS 4 // 4-pixel spans per lane: a workgroup owns 256 * 4 spans = 4096 pixels of one frame
 
 namespace {
 enum { PR_DISC = 1, PR_TRI = 2 };
@@ -233,14 +251,56 @@ __global__ __launch_bounds__(FA_RENDER_THREADS) void fa_render_kernel(FaRenderAr
 }
 } // namespace
 
-int fa_render_tiles(int size) { // workgroups per frame (the host checks K * tiles against the grid limit)
+static int fa_render_tiles(int size) { // workgroups per frame (fa_render checks K * tiles against the grid limit)
     const long long total = (long long)size * ((size + 3) >> 2);
     const int per_wg = FA_RENDER_THREADS * FA_RENDER_QUADS;
     return (int)((total + per_wg - 1) / per_wg);
 }
 
-hipError_t fa_launch_render(const FaRenderArgs &a, hipStream_t st) {
+static hipError_t fa_launch_render(const FaRenderArgs &a, hipStream_t st) {
     const int tiles = fa_render_tiles(a.size);
     hipLaunchKernelGGL(fa_render_kernel, dim3((unsigned)((long long)a.K * tiles)), dim3(FA_RENDER_THREADS), 0, st, a, tiles);
     return hipGetLastError();
+}
+
+extern "C" int fa_render(fa_env *env, const fa_render_io *io, void *stream) {
+    FA_ENTER(env, "fa_render", false, io);
+    if (!io->env_index || !io->rgb) return fail(FA_ERR_INVALID, "fa_render: env_index and rgb are required");
+    if (io->num_frames < 1) return fail(FA_ERR_INVALID, "fa_render: num_frames must be >= 1");
+    if (io->size < 8 || io->size > 2048) return fail(FA_ERR_INVALID, "fa_render: size must be 8..2048");
+    if ((io->team_attn != nullptr) != (io->opp_attn != nullptr))
+        return fail(FA_ERR_INVALID, "fa_render: team_attn and opp_attn go together (the guards' pair, or neither)");
+    if ((long long)io->num_frames * fa_render_tiles(io->size) > 0x7fffffffLL)
+        return fail(FA_ERR_INVALID, "fa_render: num_frames x size is more than one launch covers");
+    FaRenderArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.s = env->s;
+    a.env_index = io->env_index;
+    a.rgb = io->rgb;
+    a.actions = io->actions;
+    a.as_e = io->act_stride_env;
+    a.as_i = io->act_stride_agent;
+    a.no_laser = io->no_laser;
+    a.team_attn = io->team_attn;
+    a.opp_attn = io->opp_attn;
+    a.K = io->num_frames;
+    a.size = io->size;
+    a.E = env->cfg.num_envs;
+    a.G = env->cfg.num_guards;
+    a.A = env->cfg.num_attackers;
+    a.viz_dead = io->viz_dead != 0;
+    a.attn_on = io->team_attn && io->viz_attn != 0;
+    const FaDerived &c = env->c;
+    a.agent_size = c.agent_size;
+    a.fort_dim = c.fort_dim;
+    a.door_x = c.door_x;
+    a.door_y = c.door_y;
+    a.wall_xmin = c.wall_xmin;
+    a.wall_xmax = c.wall_xmax;
+    a.wall_ymin = c.wall_ymin;
+    a.wall_ymax = c.wall_ymax;
+    a.shoot_rad = c.shoot_rad;
+    a.half_win = c.half_win;
+    FA_HIP(fa_launch_render(a, static_cast<hipStream_t>(stream)));
+    return FA_OK;
 }

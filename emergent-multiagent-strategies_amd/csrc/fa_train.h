@@ -1,4 +1,4 @@
-// fa_train.h -- internal declarations of the fused PPO minibatch kernel (fa_train.hip): the MPNN forward, the
+// fa_train.h -- the buffer layouts of the fused PPO minibatch kernel (fa_train.hip, fa_train_dw.hip): the MPNN forward, the
 // alive-masked PPO losses and the complete backward pass of one team's minibatch in one launch.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -66,49 +66,7 @@
 #define FA_DWA_FLOATS (256 * 128 + 128 * 128)
 #define FA_DWB_FLOATS (128 * 256 + 2 * 64 * 64)
 
-// One launch of fa_train_kernel covers the whole minibatch: workgroup t differentiates tile t and owns slot t of mslab /
-// rec_a / rec_b / rec_g (handing the records to the weight-gradient GEMM in chunks measured slower: DESIGN 3.6).
-struct FaTrainArgs {
-    const float *obs;          // (B, N, 6) minibatch observations
-    const int64_t *action;     // (B, N) the actions taken (own agents' columns are read)
-    const float *value_pred;   // (B, N) value_preds of the rollout
-    const float *ret;          // (B, N) returns
-    const float *old_logp;     // (B, N) action_log_probs of the rollout
-    const float *adv;          // (B, N) normalised advantages, or null with adv_mean / adv_std
-    const double *adv_mean, *adv_std; // per agent (N): the kernel normalises ret - value_pred itself (ppo.py:121-124)
-    const int64_t *idx;        // the minibatch: sample b is row idx[b] of the six arrays above (null: row b)
-    const float *w;            // forward pack (FA_POFF_*)
-    const float *wt;           // transposed pack (FA_TOFF_*)
-    float *mslab;              // [tiles][FA_MSLAB_FLOATS]
-    float *rec_a;              // [tiles][3][FA_RECA_FLOATS]
-    float *rec_b;              // [tiles][FA_RECB_FLOATS]
-    float *rec_g;              // [tiles][3][FA_REC_PLANE]
-    int32_t B, G, A, team;     // team 0: the guards' policy on the guards' rows; 1: the attackers'
-    const float *mask_part;    // with scale == null: FA_MASK_PARTS partial alive-mask sums (fa_launch_mask_parts); the
-    float *scale_out;          // kernel derives the scale pair itself (`normalize`: divide by the mask mean) and
-    int32_t normalize;         // workgroup 0 leaves it at scale_out[0..1]
-    const float *scale;        // device float[2]: {1 / (B n mask_mean'), mask_mean'} with mask_mean' = the alive-mask
-                               // mean of the minibatch (1 where that is 0, or when the caller normalises later:
-                               // several ranks).  [0] multiplies every loss gradient; [1] undoes it for the
-                               // unclipped value loss, which the reference does not mask (ppo.py:178-182)
-    float clip;                // PPO clip parameter
-    float c_value, c_entropy;  // loss coefficients
-    int32_t clipped_value_loss;
-};
-
-hipError_t fa_launch_tasks(const fa_task *tasks, int n, hipStream_t st);
-hipError_t fa_launch_pack(const float *plain, float *w, float *wt, hipStream_t st);
-int fa_train_tile_envs(int G, int A);
-hipError_t fa_launch_train(const FaTrainArgs &a, hipStream_t st);
-// FA_MASK_PARTS partial sums of the alive mask over the minibatch's own-team rows (FaTrainArgs::mask_part)
-hipError_t fa_launch_mask_parts(const FaTrainArgs &a, float *part, hipStream_t st);
-// Adam (torch.optim.Adam, no amsgrad / weight decay) on flat buffers after the global-norm clip of
-// nn.utils.clip_grad_norm_: two launches.  seg: nseg + 1 offsets; steps: nseg step counters (float);
-// scratch: FA_ADAM_SCRATCH floats, 16-byte aligned ([0] receives the clip coefficient); hyper: null, or 5 device
-// floats (lr, beta1, beta2, eps, max_norm) that replace the by-value arguments at run time
-hipError_t fa_launch_adam(float *p, float *g, float *m, float *v, float *steps, const int32_t *seg, int nseg, int n, float lr,
-                          float beta1, float beta2, float eps, float max_norm, float *scratch, const float *hyper,
-                          hipStream_t st);
+// what fa_train.hip launches from fa_train_dw.hip
 // The weight-gradient GEMMs over the records of `tiles` tiles -> FA_DW_WGS_A + FA_DW_WGS_B partial slabs at dw_slabs
 hipError_t fa_launch_train_dw(const float *rec_a, const float *rec_b, int tiles, float *dw_slabs, hipStream_t st);
 // mslab of `tiles` tiles -> mpart[FA_MRED_PARTS][FA_MSLAB_FLOATS]; then out[k], k < FA_SLAB_LOSS + 8, from the partial

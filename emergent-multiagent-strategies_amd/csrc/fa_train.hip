@@ -32,7 +32,39 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fa_env.h"
 #include "fa_train.h"
+
+// One launch of fa_train_kernel covers the whole minibatch: workgroup t differentiates tile t and owns slot t of mslab /
+// rec_a / rec_b / rec_g (handing the records to the weight-gradient GEMM in chunks measured slower: DESIGN 3.6).
+struct FaTrainArgs {
+    const float *obs;          // (B, N, 6) minibatch observations
+    const int64_t *action;     // (B, N) the actions taken (own agents' columns are read)
+    const float *value_pred;   // (B, N) value_preds of the rollout
+    const float *ret;          // (B, N) returns
+    const float *old_logp;     // (B, N) action_log_probs of the rollout
+    const float *adv;          // (B, N) normalised advantages, or null with adv_mean / adv_std
+    const double *adv_mean, *adv_std; // per agent (N): the kernel normalises ret - value_pred itself (ppo.py:121-124)
+    const int64_t *idx;        // the minibatch: sample b is row idx[b] of the six arrays above (null: row b)
+    const float *w;            // forward pack (FA_POFF_*)
+    const float *wt;           // transposed pack (FA_TOFF_*)
+    float *mslab;              // [tiles][FA_MSLAB_FLOATS]
+    float *rec_a;              // [tiles][3][FA_RECA_FLOATS]
+    float *rec_b;              // [tiles][FA_RECB_FLOATS]
+    float *rec_g;              // [tiles][3][FA_REC_PLANE]
+    int32_t B, G, A, team;     // team 0: the guards' policy on the guards' rows; 1: the attackers'
+    const float *mask_part;    // with scale == null: FA_MASK_PARTS partial alive-mask sums (fa_launch_mask_parts); the
+    float *scale_out;          // kernel derives the scale pair itself (`normalize`: divide by the mask mean) and
+    int32_t normalize;         // workgroup 0 leaves it at scale_out[0..1]
+    const float *scale;        // device float[2]: {1 / (B n mask_mean'), mask_mean'} with mask_mean' = the alive-mask
+                               // mean of the minibatch (1 where that is 0, or when the caller normalises later:
+                               // several ranks).  [0] multiplies every loss gradient; [1] undoes it for the
+                               // unclipped value loss, which the reference does not mask (ppo.py:178-182)
+    float clip;                // PPO clip parameter
+    float c_value, c_entropy;  // loss coefficients
+    int32_t clipped_value_loss;
+};
+
 // weights requested four 16-byte steps ahead per lane (fa_policy.hip: eight): with one accumulator tile per wave and the
 // backward's operands in flight the tile kernel is at its register limit, and the shorter chunk spills less
 // (A/B: 754 -> 710 us per fa_ppo_grad call, 0.191 -> 0.180 s per update)
@@ -833,9 +865,9 @@ __global__ __launch_bounds__(256) void fa_adam_kernel(float *__restrict__ p, flo
 }
 } // namespace
 
-int fa_train_tile_envs(int G, int A) { return TR / (G > A ? G : A); }
+static int fa_train_tile_envs(int G, int A) { return TR / (G > A ? G : A); }
 
-hipError_t fa_launch_train(const FaTrainArgs &a, hipStream_t st) {
+static hipError_t fa_launch_train(const FaTrainArgs &a, hipStream_t st) {
     const int ET = fa_train_tile_envs(a.G, a.A);
     const dim3 grid((a.B + ET - 1) / ET), block(NTH);
     const int big = a.G > a.A ? a.G : a.A;
@@ -851,17 +883,106 @@ hipError_t fa_launch_train(const FaTrainArgs &a, hipStream_t st) {
     return hipGetLastError();
 }
 
-hipError_t fa_launch_mask_parts(const FaTrainArgs &a, float *part, hipStream_t st) {
+// FA_MASK_PARTS partial sums of the alive mask over the minibatch's own-team rows (FaTrainArgs::mask_part)
+static hipError_t fa_launch_mask_parts(const FaTrainArgs &a, float *part, hipStream_t st) {
     hipLaunchKernelGGL(fa_mask_part_kernel, dim3(FA_MASK_PARTS), dim3(64), 0, st, a, part);
     return hipGetLastError();
 }
 
-hipError_t fa_launch_adam(float *p, float *g, float *m, float *v, float *steps, const int32_t *seg, int nseg, int n,
-                          float lr, float beta1, float beta2, float eps, float max_norm, float *scratch, const float *hyper,
-                          hipStream_t st) {
+// Adam (torch.optim.Adam, no amsgrad / weight decay) on flat buffers after the global-norm clip of
+// nn.utils.clip_grad_norm_: two launches.  seg: nseg + 1 offsets; steps: nseg step counters (float);
+// scratch: FA_ADAM_SCRATCH floats, 16-byte aligned ([0] receives the clip coefficient); hyper: null, or 5 device
+// floats (lr, beta1, beta2, eps, max_norm) that replace the by-value arguments at run time
+static hipError_t fa_launch_adam(float *p, float *g, float *m, float *v, float *steps, const int32_t *seg, int nseg, int n,
+                                 float lr, float beta1, float beta2, float eps, float max_norm, float *scratch, const float *hyper,
+                                 hipStream_t st) {
     hipLaunchKernelGGL(fa_sqnorm_part_kernel, dim3(FA_NORM_PARTS), dim3(64), 0, st, g, n, reinterpret_cast<double *>(scratch + 4),
                        steps, nseg);
     hipLaunchKernelGGL(fa_adam_kernel, dim3((n + 255) / 256), dim3(256), 0, st, p, g, m, v, steps, seg, nseg, lr, beta1, beta2,
                        eps, max_norm, scratch, hyper);
     return hipGetLastError();
 }
+
+extern "C" {
+
+int64_t fa_ppo_grad_floats(void) { return FA_SLAB_FLOATS; }
+int64_t fa_adam_scratch_floats(void) { return FA_ADAM_SCRATCH; }
+int64_t fa_policy_weight_t_floats(void) { return FA_TRANS_FLOATS; }
+
+int fa_ppo_grad_scratch(int32_t B, int32_t G, int32_t A, int64_t *slab_floats, int64_t *hsave_floats) {
+    if (B < 1 || G < 1 || A < 1 || G > FA_POLICY_MAX_TEAM || A > FA_POLICY_MAX_TEAM)
+        return fail(FA_ERR_INVALID, "fa_ppo_grad_scratch: need B >= 1 and teams of 1..8");
+    const int et = fa_train_tile_envs(G, A);
+    const int64_t tiles = (B + et - 1) / et;
+    // slabs: the tiles' small gradients | their stage-1 sums | the partial slabs of the weight-gradient GEMM | mask sums
+    if (slab_floats) *slab_floats = tiles * FA_MSLAB_FLOATS + (int64_t)FA_MRED_PARTS * FA_MSLAB_FLOATS +
+                                    (int64_t)FA_DW_WGS_A * FA_DWA_FLOATS + (int64_t)FA_DW_WGS_B * FA_DWB_FLOATS + FA_MASK_PARTS;
+    // hsave: the records of the weight-gradient GEMM's operands: [tiles][3] x A, then [tiles] x B
+    if (hsave_floats) *hsave_floats = tiles * FA_TR_SAVE_FLOATS;
+    return FA_OK;
+}
+
+int fa_ppo_grad(const fa_ppo_grad_io *io, void *stream) {
+    if (!io) return fail(FA_ERR_INVALID, "fa_ppo_grad: null io");
+    if (!io->obs || !io->action || !io->value_pred || !io->ret || !io->old_log_prob || !io->weights ||
+        !io->weights_t || !io->slabs || !io->hsave || !io->out)
+        return fail(FA_ERR_INVALID, "fa_ppo_grad: every pointer but idx, scale and adv / adv_mean / adv_std is required");
+    if ((io->adv_mean == nullptr) != (io->adv_std == nullptr) || (!io->adv && !io->adv_mean))
+        return fail(FA_ERR_INVALID, "fa_ppo_grad: pass adv, or adv_mean and adv_std together");
+    if (io->B < 1 || io->num_guards < 1 || io->num_attackers < 1 || io->num_guards > FA_POLICY_MAX_TEAM ||
+        io->num_attackers > FA_POLICY_MAX_TEAM || (io->team != 0 && io->team != 1))
+        return fail(FA_ERR_INVALID, "fa_ppo_grad: need B >= 1, teams of 1..8, team 0 or 1");
+    FaTrainArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.obs = io->obs; a.action = io->action; a.value_pred = io->value_pred; a.ret = io->ret;
+    a.old_logp = io->old_log_prob; a.adv = io->adv; a.w = io->weights; a.wt = io->weights_t;
+    a.adv_mean = io->adv_mean; a.adv_std = io->adv_std;
+    a.scale = io->scale; a.idx = io->idx;
+    a.B = io->B; a.G = io->num_guards; a.A = io->num_attackers; a.team = io->team;
+    a.clip = io->clip_param; a.c_value = io->value_loss_coef; a.c_entropy = io->entropy_coef;
+    a.clipped_value_loss = io->clipped_value_loss;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int et = fa_train_tile_envs(a.G, a.A);
+    const size_t tiles = (size_t)((a.B + et - 1) / et);
+    float *mpart = io->slabs + tiles * FA_MSLAB_FLOATS, *dw_slabs = mpart + (size_t)FA_MRED_PARTS * FA_MSLAB_FLOATS;
+    a.mslab = io->slabs;
+    a.rec_a = io->hsave;
+    a.rec_b = io->hsave + tiles * 3 * FA_RECA_FLOATS;
+    a.rec_g = a.rec_b + tiles * FA_RECB_FLOATS;
+    if (!a.scale) { // partial mask sums behind the partial slabs; the scale pair is left behind the loss sums of `out`
+        float *part = dw_slabs + (size_t)FA_DW_WGS_A * FA_DWA_FLOATS + (size_t)FA_DW_WGS_B * FA_DWB_FLOATS;
+        FA_HIP(fa_launch_mask_parts(a, part, s));
+        a.mask_part = part;
+        a.scale_out = io->out + FA_SLAB_LOSS + 8;
+        a.normalize = io->normalize != 0;
+    }
+    FA_HIP(fa_launch_train(a, s));                                           // tiles: forward, losses, dL/dX
+    FA_HIP(fa_launch_train_dw(a.rec_a, a.rec_b, (int)tiles, dw_slabs, s));   // dW = X^T dY over all rows
+    FA_HIP(fa_launch_train_reduce(a.mslab, (int)tiles, mpart, dw_slabs, io->out, s)); // fixed-order sums -> out
+    return FA_OK;
+}
+
+int fa_adam_step(float *params, float *grads, float *exp_avg, float *exp_avg_sq, float *steps, const int32_t *seg,
+                 int32_t nseg, int32_t n, float lr, float beta1, float beta2, float eps, float max_grad_norm, float *scratch,
+                 void *stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !steps || !seg || !scratch)
+        return fail(FA_ERR_INVALID, "fa_adam_step: null argument");
+    if (nseg < 1 || n < 1) return fail(FA_ERR_INVALID, "fa_adam_step: need nseg >= 1 and n >= 1");
+    if (reinterpret_cast<uintptr_t>(scratch) & 15) return fail(FA_ERR_INVALID, "fa_adam_step: scratch must be 16-byte aligned");
+    FA_HIP(fa_launch_adam(params, grads, exp_avg, exp_avg_sq, steps, seg, nseg, n, lr, beta1, beta2, eps, max_grad_norm, scratch,
+                          nullptr, static_cast<hipStream_t>(stream)));
+    return FA_OK;
+}
+
+int fa_adam_step_dev(float *params, float *grads, float *exp_avg, float *exp_avg_sq, float *steps, const int32_t *seg,
+                     int32_t nseg, int32_t n, const float *hyper, float *scratch, void *stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !steps || !seg || !scratch || !hyper)
+        return fail(FA_ERR_INVALID, "fa_adam_step_dev: null argument");
+    if (nseg < 1 || n < 1) return fail(FA_ERR_INVALID, "fa_adam_step_dev: need nseg >= 1 and n >= 1");
+    if (reinterpret_cast<uintptr_t>(scratch) & 15) return fail(FA_ERR_INVALID, "fa_adam_step_dev: scratch must be 16-byte aligned");
+    FA_HIP(fa_launch_adam(params, grads, exp_avg, exp_avg_sq, steps, seg, nseg, n, 0.f, 0.f, 0.f, 0.f, 0.f, scratch, hyper,
+                          static_cast<hipStream_t>(stream)));
+    return FA_OK;
+}
+
+} // extern "C"

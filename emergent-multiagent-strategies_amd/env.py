@@ -85,13 +85,17 @@ class BatchedFortAttack(object):
                    "fa_reset")
         return obs_f32 if obs_f32 is not None else obs_f64
 
+    def _step_shapes(self, lead=()):
+        """(shape, dtype) of every output of fa_step_io; `lead`: the leading step dimension of a several-step launch."""
+        EN = lead + (self.E, self.N)
+        return dict(obs_f32=(EN + (6,), torch.float32), reward_f32=(EN, torch.float32), mask_f32=(EN, torch.float32),
+                    done=(lead + (self.E,), torch.uint8), obs_f64=(EN + (6,), torch.float64), reward_f64=(EN, torch.float64),
+                    hit=(EN, torch.uint8), was_hit=(EN, torch.uint8))
+
     def step(self, actions, auto_reset=True, out=None, want=("obs_f32", "reward_f32", "mask_f32", "done")):
         """fa_step.  actions: int64 device tensor (E, N) (any strides).  Returns dict."""
         assert actions.dtype == torch.int64 and actions.is_cuda and tuple(actions.shape) == (self.E, self.N)
-        shapes = dict(obs_f32=((self.E, self.N, 6), torch.float32), reward_f32=((self.E, self.N), torch.float32),
-                      mask_f32=((self.E, self.N), torch.float32), done=((self.E,), torch.uint8),
-                      obs_f64=((self.E, self.N, 6), torch.float64), reward_f64=((self.E, self.N), torch.float64),
-                      hit=((self.E, self.N), torch.uint8), was_hit=((self.E, self.N), torch.uint8))
+        shapes = self._step_shapes()
         out = dict(out or {})
         for k in want:
             if k not in out:
@@ -113,10 +117,7 @@ class BatchedFortAttack(object):
         device tensor (T, E, N) (any strides); every output gets a leading T dimension."""
         assert actions.dtype == torch.int64 and actions.is_cuda and tuple(actions.shape[1:]) == (self.E, self.N)
         T = actions.shape[0]
-        shapes = dict(obs_f32=((T, self.E, self.N, 6), torch.float32), reward_f32=((T, self.E, self.N), torch.float32),
-                      mask_f32=((T, self.E, self.N), torch.float32), done=((T, self.E), torch.uint8),
-                      obs_f64=((T, self.E, self.N, 6), torch.float64), reward_f64=((T, self.E, self.N), torch.float64),
-                      hit=((T, self.E, self.N), torch.uint8), was_hit=((T, self.E, self.N), torch.uint8))
+        shapes = self._step_shapes((T,))
         out = {k: self._new(*shapes[k]) for k in want}
         io = _lib.StepIO()
         io.actions = _ptr(actions)
@@ -168,13 +169,17 @@ class BatchedFortAttack(object):
     def gae(self, gamma=0.99, tau=0.95):
         _lib.check(self._lib.fa_gae(self._h, float(gamma), float(tau), _stream()), "fa_gae")
 
+    def _stat_buffers(self):
+        """The handle's own float64 result buffers of the advantage statistics, made at first use and kept (a captured graph
+        replays onto the same addresses): _gae_mom (N,3) {n, mean, M2}, _adv_ms (2,N) mean / std."""
+        if not hasattr(self, "_adv_ms"):
+            self._gae_mom = torch.zeros((self.N, 3), dtype=torch.float64, device=self.device)
+            self._adv_ms = torch.zeros((2, self.N), dtype=torch.float64, device=self.device)
+
     def gae_moments(self, gamma=0.99, tau=0.95):
         """fa_gae_moments: GAE, then the per-agent advantage moments in one pass.  Returns (moments (N,3)
         {n, mean, M2}, mean (N,), std (N,)) of this handle's samples, float64 on device."""
-        if not hasattr(self, "_gae_mom"):
-            self._gae_mom = torch.zeros((self.N, 3), dtype=torch.float64, device=self.device)
-        if not hasattr(self, "_adv_ms"):
-            self._adv_ms = torch.zeros((2, self.N), dtype=torch.float64, device=self.device)
+        self._stat_buffers()
         _lib.check(self._lib.fa_gae_moments(self._h, float(gamma), float(tau), _ptr(self._gae_mom),
                                             _ptr(self._adv_ms[0]), _ptr(self._adv_ms[1]), _stream()), "fa_gae_moments")
         return self._gae_mom, self._adv_ms[0], self._adv_ms[1]
@@ -183,10 +188,7 @@ class BatchedFortAttack(object):
         """fa_gae_normalize: the collector tail of one rank in two launches -- GAE + moment partials, fold + normalisation
         (ppo.py:121-124).  Returns (adv (T, E, N, 1) float32, moments (N,3), mean (N,), std (N,)); == gae_moments() +
         adv_normalize() bit for bit."""
-        if not hasattr(self, "_gae_mom"):
-            self._gae_mom = torch.zeros((self.N, 3), dtype=torch.float64, device=self.device)
-        if not hasattr(self, "_adv_ms"):
-            self._adv_ms = torch.zeros((2, self.N), dtype=torch.float64, device=self.device)
+        self._stat_buffers()
         if out is None:
             out = self._new((self.storage.num_steps, self.E, self.N, 1), torch.float32)
         _lib.check(self._lib.fa_gae_normalize(self._h, float(gamma), float(tau), _ptr(out), _ptr(self._gae_mom),
@@ -195,10 +197,7 @@ class BatchedFortAttack(object):
 
     def adv_moments_onepass(self):
         """fa_adv_moments_onepass: the statistics half of gae_moments alone (same buffers, same values), on the current stream."""
-        if not hasattr(self, "_gae_mom"):
-            self._gae_mom = torch.zeros((self.N, 3), dtype=torch.float64, device=self.device)
-        if not hasattr(self, "_adv_ms"):
-            self._adv_ms = torch.zeros((2, self.N), dtype=torch.float64, device=self.device)
+        self._stat_buffers()
         _lib.check(self._lib.fa_adv_moments_onepass(self._h, _ptr(self._gae_mom), _ptr(self._adv_ms[0]), _ptr(self._adv_ms[1]),
                                                     _stream()), "fa_adv_moments_onepass")
         return self._gae_mom, self._adv_ms[0], self._adv_ms[1]
@@ -213,8 +212,7 @@ class BatchedFortAttack(object):
 
     def adv_mean_std(self):
         """fa_adv_mean_std: per-agent mean / unbiased std of this handle's advantages (N,), on device."""
-        if not hasattr(self, "_adv_ms"):
-            self._adv_ms = torch.zeros((2, self.N), dtype=torch.float64, device=self.device)
+        self._stat_buffers()
         _lib.check(self._lib.fa_adv_mean_std(self._h, _ptr(self._adv_ms[0]), _ptr(self._adv_ms[1]), _stream()),
                    "fa_adv_mean_std")
         return self._adv_ms[0], self._adv_ms[1]
@@ -229,8 +227,7 @@ class BatchedFortAttack(object):
     def adv_merge(self, gathered):
         """fa_adv_merge: gathered (world, N, 3) -> global (mean, std), each (N,)."""
         assert gathered.is_contiguous() and gathered.dtype == torch.float64 and gathered.shape[1:] == (self.N, 3)
-        if not hasattr(self, "_adv_ms"):
-            self._adv_ms = torch.zeros((2, self.N), dtype=torch.float64, device=self.device)
+        self._stat_buffers()
         _lib.check(self._lib.fa_adv_merge(self._h, _ptr(gathered), int(gathered.shape[0]), _ptr(self._adv_ms[0]),
                                           _ptr(self._adv_ms[1]), _stream()), "fa_adv_merge")
         return self._adv_ms[0], self._adv_ms[1]
@@ -245,8 +242,7 @@ class BatchedFortAttack(object):
     def adv_merge_normalize(self, gathered, out=None):
         """fa_adv_merge_normalize: the several-rank tail behind the all-gather in one launch -- merge of the gathered (W, N, 3)
         moments + normalisation.  Returns (adv, mean, std); == adv_merge() + adv_normalize() bit for bit."""
-        if not hasattr(self, "_adv_ms"):
-            self._adv_ms = torch.zeros((2, self.N), dtype=torch.float64, device=self.device)
+        self._stat_buffers()
         if out is None:
             out = self._new((self.storage.num_steps, self.E, self.N, 1), torch.float32)
         _lib.check(self._lib.fa_adv_merge_normalize(self._h, _ptr(gathered), int(gathered.shape[0]), _ptr(out),

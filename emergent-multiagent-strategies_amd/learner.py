@@ -66,6 +66,23 @@ def _capture_mode():
     return "thread_local" if (dist.is_available() and dist.is_initialized()) else "global"
 
 
+def _warm_state(eng, storage, G, A):
+    """A harmless world for the warm-up steps ahead of a graph capture (BatchedLearner, CrossPlay): teams on opposite walls
+    facing away from each other (no laser can hit, nobody is near the door, no timeout), so no episode ends and the reset
+    RNG stream is not touched."""
+    import numpy as np
+    E, N = eng.E, eng.N
+    x = np.concatenate([np.linspace(-0.9, 0.9, G), np.linspace(-0.9, 0.9, A)])
+    y = np.concatenate([np.full(G, 0.6), np.full(A, -0.6)])
+    ang = np.concatenate([np.full(G, np.pi / 2), np.full(A, 3 * np.pi / 2)])
+    tile = lambda v: np.tile(v[None, :], (E, 1))
+    eng.set_state(dict(pos_x=tile(x), pos_y=tile(y), vel_x=np.zeros((E, N)), vel_y=np.zeros((E, N)),
+                       ang=tile(ang), prev_dist=np.full((E, N), np.nan),
+                       alive=np.ones((E, N), np.uint8), time_step=np.zeros(E, np.int32)))
+    obs = np.stack([np.ones((E, N)), tile(x), tile(y), tile(ang), np.zeros((E, N)), np.zeros((E, N))], -1)
+    storage.obs[:2] = torch.from_numpy(obs.astype(np.float32)).to(storage.obs.device)
+
+
 def finish_exchange_(flat, n, world):
     """The arithmetic behind an optimizer step's all-reduce, in place on the summed flat buffer
     [gradients (n floats) | 3 loss sums | alive-mask mean | ...]: the mean over the ranks (equal shard sizes: == the union
@@ -623,22 +640,6 @@ class BatchedLearner(object):
         #  sample_attacker() after every episode-end reset, train_fortattack_v2.py:104-111)
         self.eng.collect_step(s, auto_reset=True)
 
-    def _warm_state(self):
-        """A harmless world for the capture warm-up steps: teams on opposite walls facing
-        away from each other (no laser can hit, nobody is near the door, no timeout), so no
-        episode ends and the reset RNG stream is not touched."""
-        import numpy as np
-        E, N, G = self.E, self.N, self.G
-        x = np.concatenate([np.linspace(-0.9, 0.9, G), np.linspace(-0.9, 0.9, self.A)])
-        y = np.concatenate([np.full(G, 0.6), np.full(self.A, -0.6)])
-        ang = np.concatenate([np.full(G, np.pi / 2), np.full(self.A, 3 * np.pi / 2)])
-        tile = lambda v: np.tile(v[None, :], (E, 1))
-        self.eng.set_state(dict(pos_x=tile(x), pos_y=tile(y), vel_x=np.zeros((E, N)), vel_y=np.zeros((E, N)),
-                                ang=tile(ang), prev_dist=np.full((E, N), np.nan),
-                                alive=np.ones((E, N), np.uint8), time_step=np.zeros(E, np.int32)))
-        obs = np.stack([np.ones((E, N)), tile(x), tile(y), tile(ang), np.zeros((E, N)), np.zeros((E, N))], -1)
-        self.storage.obs[:2] = torch.from_numpy(obs.astype(np.float32)).to(self.device)
-
     @torch.no_grad()
     def _value_last(self):
         """wrap_horizon: V(obs[T]) -> value_preds[T] (learner.py:196-202)."""
@@ -661,7 +662,7 @@ class BatchedLearner(object):
         """ONE hipGraph for the whole rollout: T x (act + env step) and V(obs[T]) -- every launch argument
         is a fixed pointer into the rollout buffers, so the T steps are T different node sets."""
         import numpy as np
-        self._warm_state()
+        _warm_state(self.eng, self.storage, self.G, self.A)
         side = torch.cuda.Stream(self.device)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):

@@ -5,16 +5,18 @@ usage: build_variant.py <name> <tu.hip> [--src other_source.hip] [--also other_t
        build_variant.py <name> --add experiments/fa_step_experiments.hip [extra hipcc flags ...]
          (the product objects PLUS one more translation unit: the library with the round-4 experiment step kernels)
 A/B the results on the GPU box with tools/ab_step.py / ab_policy.py / ab_train.py."""
+import importlib.util
 import os
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "emergent-multiagent-strategies_amd", "csrc")
-OBJ = os.path.join(CSRC, "_obj")
-SOURCES = ["fa_step_pipe.hip", "fa_step_classic.hip", "fa_collect.hip", "fa_policy.hip", "fa_match.hip", "fa_attend.hip", "fa_train.hip", "fa_train_dw.hip", "fa_fold.hip", "fa_rccl.hip", "fa_api.hip"]
-import shutil
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+# the translation units, their objects and the compiler are the product build's: build.py, loaded by path (the package itself
+# need not import)
+_spec = importlib.util.spec_from_file_location("_fa_build", os.path.join(ROOT, "emergent-multiagent-strategies_amd", "build.py"))
+_build = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(_build)
+CSRC, OBJ, SOURCES, HIPCC = _build.CSRC, _build.OBJ, _build.SOURCES, _build.hipcc()
 name, tu = sys.argv[1], sys.argv[2]
 extra = sys.argv[3:]
 add = tu == "--add"
