@@ -79,10 +79,16 @@ __device__ __forceinline__ void pack_x3(float x, float *__restrict__ w, int dst3
     w16[base + 2 * 64 * 8] = (uint16_t)(l >> 16);
 }
 __global__ __launch_bounds__(256) void fa_pack_kernel(const float *__restrict__ plain, float *__restrict__ w, float *__restrict__ wt) {
-    const int dst3[6] = {FA_POFF3_AO, FA_POFF3_BO, FA_POFF3_AM, FA_POFF3_W7, FA_POFF3_W8, FA_POFF3_W9};
-    const PackSpec fwd[6] = {{FA_POFF_AO, 64, 64, FA_POFF_AO}, {FA_POFF_BO, 64, 64, FA_POFF_BO}, {FA_POFF_AM, 128, 128, FA_POFF_AM},
-                             {FA_POFF_W7, 256, 128, FA_POFF_W7}, {FA_POFF_W8, 128, 256, FA_POFF_W8}, {FA_POFF_W9, 256, 32, FA_POFF_W9}};
-    const int tdst[6] = {FA_TOFF_AOT, FA_TOFF_BOT, FA_TOFF_AMT, FA_TOFF_W7T, FA_TOFF_W8T, FA_TOFF_W9T};
+    // the dense sections (fa_policy.h FA_DENSE_SECTIONS): bf16x3 offset, forward spec, transposed offset
+#define FA_X3(n, K, C) FA_POFF3_##n,
+#define FA_XF(n, K, C) {FA_POFF_##n, K, C, FA_POFF_##n},
+#define FA_XT(n, K, C) FA_TOFF_##n##T,
+    const int dst3[6] = {FA_DENSE_SECTIONS(FA_X3)};
+    const PackSpec fwd[6] = {FA_DENSE_SECTIONS(FA_XF)};
+    const int tdst[6] = {FA_DENSE_SECTIONS(FA_XT)};
+#undef FA_X3
+#undef FA_XF
+#undef FA_XT
     const int g = blockIdx.x * 256 + threadIdx.x;
     // the un-packed sections (encoders, biases) are copied as they are
     if (g < FA_POFF_AO) w[g] = plain[g];

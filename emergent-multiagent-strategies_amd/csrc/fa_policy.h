@@ -39,3 +39,26 @@
 #define FA_POFF3_W8 185632  // (128 x 256)
 #define FA_POFF3_W9 234784  // (256 x 32)
 #define FA_POLICY_WEIGHT_FLOATS 247072
+
+// The six dense sections as X(name, K, C).  The offsets above stay literals (include/fortattack.h documents them for other
+// hosts); what follows checks that each is the previous one plus the previous section's size.
+#define FA_DENSE_SECTIONS(X) X(AO, 64, 64) X(BO, 64, 64) X(AM, 128, 128) X(W7, 256, 128) X(W8, 128, 256) X(W9, 256, 32)
+static_assert(FA_POFF_WE == 0 && FA_POFF_BE == FA_POFF_WE + 6 * 64 && FA_POFF_WOE == FA_POFF_BE + 64 && FA_POFF_BOE == FA_POFF_WOE + 6 * 64 &&
+                  FA_POFF_AO == FA_POFF_BOE + 64 && FA_POFF_BO == FA_POFF_AO + 64 * 64 && FA_POFF_AM == FA_POFF_BO + 64 * 64 &&
+                  FA_POFF_W7 == FA_POFF_AM + 128 * 128 && FA_POFF_BU == FA_POFF_W7 + 256 * 128 && FA_POFF_W8 == FA_POFF_BU + 128 &&
+                  FA_POFF_B8 == FA_POFF_W8 + 128 * 256 && FA_POFF_W9 == FA_POFF_B8 + 256 && FA_POFF_B9 == FA_POFF_W9 + 256 * 32 &&
+                  FA_POLICY_PLAIN_FLOATS == FA_POFF_B9 + 32,
+              "FA_POFF_*: the float32 sections lie back to back");
+// {offset, floats} of the dense sections in some pack, in order: back to back from `at` up to `end`?
+constexpr bool fa_back_to_back(const int (*sec)[2], int n, int at, int end) {
+    for (int i = 0; i < n; ++i) {
+        if (sec[i][0] != at) return false;
+        at += sec[i][1];
+    }
+    return at == end;
+}
+#define FA_X(n, K, C) {FA_POFF3_##n, (K) * (C) * 3 / 2},
+constexpr int fa_poff3_sections[][2] = {FA_DENSE_SECTIONS(FA_X)};
+#undef FA_X
+static_assert(fa_back_to_back(fa_poff3_sections, 6, FA_POLICY_PLAIN_FLOATS, FA_POLICY_WEIGHT_FLOATS),
+              "FA_POFF3_*: 1.5 floats per weight, back to back behind the float32 sections");

@@ -18,6 +18,10 @@
 #define FA_TOFF_W8T 57344  // packed (256 x 128): W8^T
 #define FA_TOFF_W9T 90112  // packed (32 x 256):  W9^T
 #define FA_TRANS_FLOATS 98304
+#define FA_X(n, K, C) {FA_TOFF_##n##T, (K) * (C)},
+constexpr int fa_toff_sections[][2] = {FA_DENSE_SECTIONS(FA_X)};
+#undef FA_X
+static_assert(fa_back_to_back(fa_toff_sections, 6, 0, FA_TRANS_FLOATS), "FA_TOFF_*: the transposed dense sections lie back to back");
 
 // The result of fa_ppo_grad (`out`): the gradient of every kernel-facing matrix in PLAIN row-major layout at the offsets
 // of the forward pack (FA_POFF_*: We (6x64) | be | Woe | boe | A_o (64x64) | B_o | A_m (128x128) | W7 (256x128)

@@ -20,6 +20,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .mpnn_pack import kernel_params      # (mpnn_pack.py imports nothing from this file)
+
 
 class _SplitKMatmul(torch.autograd.Function):
     """y = x @ w for a tall-skinny x (tens of thousands of rows, <= 384 columns).
@@ -263,13 +265,10 @@ class MPNN(nn.Module):
     # ---- the same trunk with three pairs of consecutive linear maps multiplied out ------------------------
     def folded_weights(self):
         """A_o = norm W_key W_query^T, B_o = W_val W_out (opponent attention); A_m = norm W_query W_key^T and
-        the two halves of the update layer, the second with W_val W_out folded in (see mpnn_pack.py).  Built
-        from the parameters inside the autograd graph: gradients reach the original tensors."""
-        a, m, hd = self.oppAttn, self.messages, self.h_dim
-        uw = self.update[0].weight
-        return (a.norm_factor * (a.W_key[0] @ a.W_query[0].t()), a.W_val[0] @ a.W_out[0],
-                m.norm_factor * (m.W_query[0] @ m.W_key[0].t()), uw[:, :hd].t(),
-                (m.W_val[0] @ m.W_out[0]) @ uw[:, hd:].t())
+        the two halves of the update layer, the second with W_val W_out folded in: mpnn_pack.kernel_params, the one
+        statement of the fold.  Built from the parameters inside the autograd graph: gradients reach the original tensors."""
+        P = kernel_params(self, heads=False)
+        return P["AO"], P["BO"], P["AM"], P["W7"][:self.h_dim], P["W7"][self.h_dim:]
 
     def trunk_folded(self, own, opp):
         """own (B, n, 6), opp (B, m, 6) -> h (B, n, h_dim): the training forward of the PPO update.  Per round

@@ -11,22 +11,45 @@ factors one after the other by ~1e-6 relative -- the size of a GEMM's own summat
     W7  = [ update.weight[:, :128]^T ; messages.W_val @ messages.W_out @ update.weight[:, 128:]^T ]
                                                              h'        = relu([h | sum_j a_ij h_j] W7 + b)
 
-Dense operands are stored in the lane order of the 32x32x2 fp32 MFMA's B operand (`pack_gemm`); the
-section offsets are csrc/fa_policy.h's FA_POFF_*.  `folded_forward` evaluates the packed buffer with
-plain torch ops (CPU or GPU): it is what the CPU tests compare with MPNN.logits_value, and documents
-the kernel's arithmetic.
+`kernel_params` is the one statement of that algebra (any dtype, inside or outside autograd) and `SECTIONS` the one
+statement of the buffers' layout: every offset below is a running sum over it (csrc/fa_policy.h and fa_train.h hold the
+same numbers as FA_POFF_* / FA_POFF3_* / FA_TOFF_* and assert their own consistency; tests/test_abi_cpu.py compares the
+two).  Dense operands are stored in the lane order of the 32x32x2 fp32 MFMA's B operand (`pack_gemm`).
+`folded_forward` evaluates the packed buffer with plain torch ops (CPU or GPU): it is what the CPU tests compare with
+MPNN.logits_value, and documents the kernel's arithmetic.
 """
+import math
+
 import torch
 
 HIDDEN = 128
-# csrc/fa_policy.h
-POFF = dict(WE=0, BE=384, WOE=448, BOE=832, AO=896, BO=4992, AM=9088, W7=25472, BU=58240, W8=58368, B8=91136,
-            W9=91392, B9=99584)
-PLAIN_FLOATS = 99616          # end of the float32 sections: the layout of the plain / gradient buffers (FA_POLICY_PLAIN_FLOATS)
-# ... followed by the six dense matrices split into three bf16 terms for the bf16 matrix cores (csrc/fa_policy.h FA_POFF3_*)
-POFF3 = dict(AO=99616, BO=105760, AM=111904, W7=136480, W8=185632, W9=234784)
-WEIGHT_FLOATS = 247072        # the packed buffer (FA_POLICY_WEIGHT_FLOATS, fa_policy_weight_floats())
 MAX_TEAM = 8
+# The kernel-facing matrices in buffer order: (name, plain row-major shape, dense).  A dense one is an MFMA B operand: packed
+# in the forward buffer (float32 lane order, then once more as bf16x3) and, transposed, in the backward's buffer.
+SECTIONS = (("WE", (6, 64), False), ("BE", (64,), False), ("WOE", (6, 64), False), ("BOE", (64,), False),
+            ("AO", (64, 64), True), ("BO", (64, 64), True), ("AM", (128, 128), True), ("W7", (256, 128), True),
+            ("BU", (128,), False), ("W8", (128, 256), True), ("B8", (256,), False), ("W9", (256, 32), True), ("B9", (32,), False))
+PLAIN_SHAPES = {k: shp for k, shp, _ in SECTIONS}
+_GEMMS = tuple(k for k, _, dense in SECTIONS if dense)
+
+
+def _offsets(sizes, at=0, align=1):
+    """[(name, floats)] laid out back to back from `at` (each start rounded up to `align`) -> ({name: offset}, end)."""
+    off = {}
+    for k, n in sizes:
+        at = -(-at // align) * align
+        off[k] = at
+        at += n
+    return off, at
+
+
+# the float32 sections = the layout of the plain / gradient buffers (FA_POFF_*, FA_POLICY_PLAIN_FLOATS) ...
+POFF, PLAIN_FLOATS = _offsets((k, math.prod(shp)) for k, shp, _ in SECTIONS)
+# ... followed by the dense matrices split into three bf16 terms, 1.5 floats per weight (FA_POFF3_*, FA_POLICY_WEIGHT_FLOATS)
+POFF3, WEIGHT_FLOATS = _offsets(((k, math.prod(PLAIN_SHAPES[k]) * 3 // 2) for k in _GEMMS), PLAIN_FLOATS)
+# the transposed pack of the PPO update's kernel (csrc/fa_train.h FA_TOFF_*, FA_TRANS_FLOATS) and its gradient slab
+TOFF, TRANS_FLOATS = _offsets((k + "T", math.prod(PLAIN_SHAPES[k])) for k in _GEMMS)
+SLAB_FLOATS = PLAIN_FLOATS + 16
 
 
 def _rne_hi(x):
@@ -76,120 +99,91 @@ def supported(pol):
         pol.num_agents <= MAX_TEAM and pol.num_opp_agents <= MAX_TEAM and pol.dist.linear.out_features == 8
 
 
+def kernel_params(pol, dtype=None, heads=True):
+    """The matrices the fused kernels work with (the folded products of this file's header, the stacked heads, zero-padded
+    W9 / b9), in the parameters' dtype or in `dtype`.  With gradients enabled they are INSIDE the autograd graph of the
+    module's parameters: torch.autograd.backward on them with the kernel's gradients applies the chain rule to the
+    parameters.  The scaled products are norm * (A @ B): what the device fold computes (FlatPolicy: alpha * acc).
+    heads=False: the trunk's alone (MPNN.trunk_folded: any hidden size and number of actions)."""
+    c = (lambda t: t) if dtype is None else (lambda t: t.to(dtype))
+    a, m, hd = pol.oppAttn, pol.messages, pol.h_dim
+    uw = c(pol.update[0].weight)
+    P = dict(
+        WE=c(pol.encoder[0].weight).t(), BE=c(pol.encoder[0].bias),
+        WOE=c(pol.oppEncoder[0].weight).t(), BOE=c(pol.oppEncoder[0].bias),
+        AO=a.norm_factor * (c(a.W_key[0]) @ c(a.W_query[0]).t()), BO=c(a.W_val[0]) @ c(a.W_out[0]),
+        AM=m.norm_factor * (c(m.W_query[0]) @ c(m.W_key[0]).t()),
+        W7=torch.cat((uw[:, :hd].t(), (c(m.W_val[0]) @ c(m.W_out[0])) @ uw[:, hd:].t()), 0), BU=c(pol.update[0].bias))
+    if heads:
+        z = lambda *s: torch.zeros(*s, device=uw.device, dtype=uw.dtype)
+        P.update(
+            W8=torch.cat((c(pol.policy_head[0].weight).t(), c(pol.value_head[0].weight).t()), 1),
+            B8=torch.cat((c(pol.policy_head[0].bias), c(pol.value_head[0].bias))),
+            W9=torch.cat((torch.cat((c(pol.dist.linear.weight).t(), z(hd, 24)), 1),
+                          torch.cat((z(hd, 8), c(pol.value_head[2].weight).t(), z(hd, 23)), 1)), 0),
+            B9=torch.cat((c(pol.dist.linear.bias), c(pol.value_head[2].bias), z(23))))
+    return P
+
+
+@torch.no_grad()
+def pack_from_params(P, out_fwd, out_t=None):
+    """kernel_params() -> the forward pack (FA_POFF_*; its bf16x3 half when out_fwd has room for it) and, when asked for,
+    the transposed pack (FA_TOFF_*), in place; rounded to float32 here, once."""
+    for k in PLAIN_SHAPES:
+        v = P[k].detach()
+        flat = pack_gemm(v) if k in _GEMMS else v.reshape(-1)
+        out_fwd[POFF[k]:POFF[k] + flat.numel()].copy_(flat)
+        if k in _GEMMS and out_fwd.numel() >= WEIGHT_FLOATS:
+            x3 = pack_gemm3(v)
+            out_fwd[POFF3[k]:POFF3[k] + x3.numel()].copy_(x3)
+        if k in _GEMMS and out_t is not None:
+            flat = pack_gemm(v.t())
+            out_t[TOFF[k + "T"]:TOFF[k + "T"] + flat.numel()].copy_(flat)
+
+
 @torch.no_grad()
 def pack_policy(pol, out=None):
-    """MPNN module (mpnn.py) -> packed float32 buffer on the module's device; `out` is rewritten in
-    place when given (a captured hipGraph keeps pointing at it)."""
+    """MPNN module (mpnn.py) -> packed float32 buffer on the module's device, the fold evaluated in float64; `out` is
+    rewritten in place when given (a captured hipGraph keeps pointing at it)."""
     if not supported(pol):
         raise ValueError("the fused policy kernel needs hidden_dim = 128, 6 inputs, 8 actions and teams of <= 8")
-    d = lambda t: t.detach().double()
-    a, m = pol.oppAttn, pol.messages
-    upd_w = d(pol.update[0].weight)                                   # (128, 256)
-    sec = {
-        "WE": d(pol.encoder[0].weight).t(), "BE": d(pol.encoder[0].bias),
-        "WOE": d(pol.oppEncoder[0].weight).t(), "BOE": d(pol.oppEncoder[0].bias),
-        "AO": pack_gemm(a.norm_factor * d(a.W_key[0]) @ d(a.W_query[0]).t()),
-        "BO": pack_gemm(d(a.W_val[0]) @ d(a.W_out[0])),
-        "AM": pack_gemm(m.norm_factor * d(m.W_query[0]) @ d(m.W_key[0]).t()),
-        "W7": pack_gemm(torch.cat((upd_w[:, :HIDDEN].t(), d(m.W_val[0]) @ d(m.W_out[0]) @ upd_w[:, HIDDEN:].t()), 0)),
-        "BU": d(pol.update[0].bias),
-        "W8": pack_gemm(torch.cat((d(pol.policy_head[0].weight).t(), d(pol.value_head[0].weight).t()), 1)),
-        "B8": torch.cat((d(pol.policy_head[0].bias), d(pol.value_head[0].bias))),
-    }
-    w9 = torch.zeros(2 * HIDDEN, 32, dtype=torch.float64, device=upd_w.device)
-    w9[:HIDDEN, :8] = d(pol.dist.linear.weight).t()
-    w9[HIDDEN:, 8] = d(pol.value_head[2].weight)[0]
-    b9 = torch.zeros(32, dtype=torch.float64, device=upd_w.device)
-    b9[:8] = d(pol.dist.linear.bias)
-    b9[8] = d(pol.value_head[2].bias)[0]
-    sec["W9"], sec["B9"] = pack_gemm(w9), b9
+    P = kernel_params(pol, torch.float64)
     if out is None:
-        out = torch.zeros(WEIGHT_FLOATS, dtype=torch.float32, device=upd_w.device)
+        out = torch.zeros(WEIGHT_FLOATS, dtype=torch.float32, device=P["W7"].device)
     assert out.numel() == WEIGHT_FLOATS and out.dtype == torch.float32 and out.is_contiguous()
-    for k, v in sec.items():
-        out[POFF[k]:POFF[k] + v.numel()].copy_(v.reshape(-1).float())
-    for k, (K, C) in (("AO", (64, 64)), ("BO", (64, 64)), ("AM", (128, 128)), ("W7", (256, 128)), ("W8", (128, 256)), ("W9", (256, 32))):
-        x3 = pack_gemm3(unpack_gemm(out[POFF[k]:POFF[k] + K * C], K, C))
-        out[POFF3[k]:POFF3[k] + x3.numel()].copy_(x3)
+    pack_from_params(P, out)
     return out
+
+
+def split_plain(flat):
+    """A plain-layout buffer (the float32 sections at the POFF offsets: a FA_SLAB of gradients) -> dict of views shaped
+    like kernel_params()."""
+    return {k: flat[POFF[k]:POFF[k] + math.prod(shp)].view(*shp) for k, shp in PLAIN_SHAPES.items()}
+
+
+def _forward(P, own, opp):
+    """The network on the kernel-facing matrices P: own (B, n, 6), opp (B, m, 6) -> (B, n, 32): 8 logits, the value, zeros."""
+    n = own.shape[1]
+    h1 = torch.relu(own @ P["WE"] + P["BE"])
+    ho = torch.relu(opp @ P["WOE"] + P["BOE"])
+    att = torch.softmax((h1 @ P["AO"]) @ ho.transpose(1, 2), dim=-1)              # (B, n, m)
+    h = torch.cat((h1, (att @ ho) @ P["BO"]), dim=2)
+    diag = torch.zeros(n, n, device=own.device).fill_diagonal_(-float("inf"))
+    for _ in range(3):
+        mix = torch.softmax((h @ P["AM"]) @ h.transpose(1, 2) + diag, dim=-1) @ h if n > 1 else torch.zeros_like(h)
+        h = torch.relu(torch.cat((h, mix), dim=2) @ P["W7"] + P["BU"])
+    return torch.relu(h @ P["W8"] + P["B8"]) @ P["W9"] + P["B9"]
 
 
 @torch.no_grad()
 def folded_forward(flat, own, opp):
-    """The kernel's arithmetic on plain tensors: own (B, n, 6), opp (B, m, 6) -> logits (B, n, 8), value (B, n, 1)."""
-    sl = lambda k, n: flat[POFF[k]:POFF[k] + n]
-    n = own.shape[1]
-    h1 = torch.relu(own @ sl("WE", 384).view(6, 64) + sl("BE", 64))
-    ho = torch.relu(opp @ sl("WOE", 384).view(6, 64) + sl("BOE", 64))
-    g = h1 @ unpack_gemm(sl("AO", 4096), 64, 64)
-    att = torch.softmax(g @ ho.transpose(1, 2), dim=-1)              # (B, n, m)
-    h = torch.cat((h1, (att @ ho) @ unpack_gemm(sl("BO", 4096), 64, 64)), dim=2)
-    am, w7 = unpack_gemm(sl("AM", 16384), 128, 128), unpack_gemm(sl("W7", 32768), 256, 128)
-    diag = torch.zeros(n, n, device=own.device).fill_diagonal_(-float("inf"))
-    for _ in range(3):
-        if n == 1:
-            mix = torch.zeros_like(h)
-        else:
-            mix = torch.softmax((h @ am) @ h.transpose(1, 2) + diag, dim=-1) @ h
-        h = torch.relu(torch.cat((h, mix), dim=2) @ w7 + sl("BU", 128))
-    pv = torch.relu(h @ unpack_gemm(sl("W8", 32768), 128, 256) + sl("B8", 256))
-    out = pv @ unpack_gemm(sl("W9", 8192), 256, 32) + sl("B9", 32)
-    return out[..., :8], out[..., 8:9]
-
-
-# ---- the PPO update's fused kernel (csrc/fa_train.hip) ---------------------------------------------------------
-TOFF = dict(AOT=0, BOT=4096, AMT=8192, W7T=24576, W8T=57344, W9T=90112)     # csrc/fa_train.h
-TRANS_FLOATS = 98304
-SLAB_FLOATS = PLAIN_FLOATS + 16
-PLAIN_SHAPES = dict(WE=(6, 64), BE=(64,), WOE=(6, 64), BOE=(64,), AO=(64, 64), BO=(64, 64), AM=(128, 128), W7=(256, 128),
-                    BU=(128,), W8=(128, 256), B8=(256,), W9=(256, 32), B9=(32,))
-
-
-def kernel_params(pol):
-    """The matrices the fused kernels work with, as float32 tensors INSIDE the autograd graph of the module's
-    parameters (the folded products of this file's header, the stacked heads, zero-padded W9 / b9): calling
-    torch.autograd.backward on them with the kernel's gradients applies the chain rule to the parameters."""
-    a, m, hd = pol.oppAttn, pol.messages, pol.h_dim
-    uw = pol.update[0].weight
-    z = lambda *s: torch.zeros(*s, device=uw.device, dtype=uw.dtype)
-    w9 = torch.cat((torch.cat((pol.dist.linear.weight.t(), z(hd, 24)), 1),
-                    torch.cat((z(hd, 8), pol.value_head[2].weight.t(), z(hd, 23)), 1)), 0)
-    return dict(
-        WE=pol.encoder[0].weight.t(), BE=pol.encoder[0].bias, WOE=pol.oppEncoder[0].weight.t(), BOE=pol.oppEncoder[0].bias,
-        AO=a.norm_factor * (a.W_key[0] @ a.W_query[0].t()), BO=a.W_val[0] @ a.W_out[0],
-        AM=m.norm_factor * (m.W_query[0] @ m.W_key[0].t()),
-        W7=torch.cat((uw[:, :hd].t(), (m.W_val[0] @ m.W_out[0]) @ uw[:, hd:].t()), 0), BU=pol.update[0].bias,
-        W8=torch.cat((pol.policy_head[0].weight.t(), pol.value_head[0].weight.t()), 1),
-        B8=torch.cat((pol.policy_head[0].bias, pol.value_head[0].bias)),
-        W9=w9, B9=torch.cat((pol.dist.linear.bias, pol.value_head[2].bias, z(23))))
-
-
-_GEMMS = ("AO", "BO", "AM", "W7", "W8", "W9")
-
-
-@torch.no_grad()
-def pack_from_params(P, out_fwd, out_t):
-    """kernel_params() -> the forward pack (FA_POFF_*) and the transposed pack (FA_TOFF_*), in place."""
-    for k, v in P.items():
-        flat = pack_gemm(v.detach()) if k in _GEMMS else v.detach().reshape(-1)
-        out_fwd[POFF[k]:POFF[k] + flat.numel()].copy_(flat)
-        if k in _GEMMS and out_fwd.numel() >= WEIGHT_FLOATS:
-            x3 = pack_gemm3(v.detach())
-            out_fwd[POFF3[k]:POFF3[k] + x3.numel()].copy_(x3)
-    for k in _GEMMS:
-        flat = pack_gemm(P[k].detach().t())
-        out_t[TOFF[k + "T"]:TOFF[k + "T"] + flat.numel()].copy_(flat)
-
-
-def split_plain(flat):
-    """A FA_SLAB buffer (gradients in plain layout at the POFF offsets) -> dict of views shaped like kernel_params()."""
-    out = {}
+    """The kernel's arithmetic on the packed buffer: own (B, n, 6), opp (B, m, 6) -> logits (B, n, 8), value (B, n, 1)."""
+    P = {}
     for k, shp in PLAIN_SHAPES.items():
-        nfl = 1
-        for d in shp:
-            nfl *= d
-        out[k] = flat[POFF[k]:POFF[k] + nfl].view(*shp)
-    return out
+        sec = flat[POFF[k]:POFF[k] + math.prod(shp)]
+        P[k] = unpack_gemm(sec, *shp) if k in _GEMMS else sec.view(*shp)
+    out = _forward(P, own, opp)
+    return out[..., :8], out[..., 8:9]
 
 
 def folded_ppo_reference(P, obs, own_sl, opp_sl, action, value_pred, ret, old_logp, adv, clip, c_value, c_entropy,
@@ -197,17 +191,8 @@ def folded_ppo_reference(P, obs, own_sl, opp_sl, action, value_pred, ret, old_lo
     """Plain-torch statement of csrc/fa_train.hip (forward on the kernel-facing matrices P + the losses of
     ppo.py:146-187 WITHOUT the division by the mask mean): returns (loss, value_loss, action_loss, entropy, mask_mean)
     where loss = c_value * value_loss + action_loss - c_entropy * entropy; differentiable in P."""
-    own, opp = obs[:, own_sl], obs[:, opp_sl]
-    n = own.shape[1]
-    h1 = torch.relu(own @ P["WE"] + P["BE"])
-    ho = torch.relu(opp @ P["WOE"] + P["BOE"])
-    att = torch.softmax((h1 @ P["AO"]) @ ho.transpose(1, 2), dim=-1)
-    h = torch.cat((h1, (att @ ho) @ P["BO"]), dim=2)
-    diag = torch.zeros(n, n, device=obs.device).fill_diagonal_(-float("inf"))
-    for _ in range(3):
-        mix = torch.softmax((h @ P["AM"]) @ h.transpose(1, 2) + diag, dim=-1) @ h if n > 1 else torch.zeros_like(h)
-        h = torch.relu(torch.cat((h, mix), dim=2) @ P["W7"] + P["BU"])
-    out = torch.relu(h @ P["W8"] + P["B8"]) @ P["W9"] + P["B9"]
+    own = obs[:, own_sl]
+    out = _forward(P, own, obs[:, opp_sl])
     logp_all = torch.log_softmax(out[..., :8], dim=-1)
     value = out[..., 8:9]
     mask = own[:, :, 0:1]
@@ -225,19 +210,62 @@ def folded_ppo_reference(P, obs, own_sl, opp_sl, action, value_pred, ret, old_lo
 
 
 # ---- the module's parameters as ONE flat buffer + the fold / unfold task lists (csrc/fa_fold.hip) -----------------
-# (name, accessor, offset) in floats; what the forward uses (oppUpdate is created but never used, mpnn.py:44-45)
-_PF = (("ENC_W", lambda p: p.encoder[0].weight, 0), ("ENC_B", lambda p: p.encoder[0].bias, 384),
-       ("OENC_W", lambda p: p.oppEncoder[0].weight, 448), ("OENC_B", lambda p: p.oppEncoder[0].bias, 832),
-       ("OQ", lambda p: p.oppAttn.W_query, 896), ("OK", lambda p: p.oppAttn.W_key, 4992),
-       ("OV", lambda p: p.oppAttn.W_val, 9088), ("OO", lambda p: p.oppAttn.W_out, 13184),
-       ("MQ", lambda p: p.messages.W_query, 17280), ("MK", lambda p: p.messages.W_key, 33664),
-       ("MV", lambda p: p.messages.W_val, 50048), ("MO", lambda p: p.messages.W_out, 66432),
-       ("UW", lambda p: p.update[0].weight, 82816), ("UB", lambda p: p.update[0].bias, 115584),
-       ("V0W", lambda p: p.value_head[0].weight, 115712), ("V0B", lambda p: p.value_head[0].bias, 132096),
-       ("V2W", lambda p: p.value_head[2].weight, 132224), ("V2B", lambda p: p.value_head[2].bias, 132352),
-       ("P0W", lambda p: p.policy_head[0].weight, 132356), ("P0B", lambda p: p.policy_head[0].bias, 148740),
-       ("DW", lambda p: p.dist.linear.weight, 148868), ("DB", lambda p: p.dist.linear.bias, 149892))
-PF_FLOATS = 149900
+# (name, accessor, (rows, columns)) of what the forward uses (oppUpdate is created but never used, mpnn.py:44-45), in the
+# order of the flat buffer; every parameter starts at a multiple of 4 floats
+_PARAMS = (("ENC_W", lambda p: p.encoder[0].weight, (64, 6)), ("ENC_B", lambda p: p.encoder[0].bias, (1, 64)),
+           ("OENC_W", lambda p: p.oppEncoder[0].weight, (64, 6)), ("OENC_B", lambda p: p.oppEncoder[0].bias, (1, 64)),
+           ("OQ", lambda p: p.oppAttn.W_query, (64, 64)), ("OK", lambda p: p.oppAttn.W_key, (64, 64)),
+           ("OV", lambda p: p.oppAttn.W_val, (64, 64)), ("OO", lambda p: p.oppAttn.W_out, (64, 64)),
+           ("MQ", lambda p: p.messages.W_query, (128, 128)), ("MK", lambda p: p.messages.W_key, (128, 128)),
+           ("MV", lambda p: p.messages.W_val, (128, 128)), ("MO", lambda p: p.messages.W_out, (128, 128)),
+           ("UW", lambda p: p.update[0].weight, (128, 256)), ("UB", lambda p: p.update[0].bias, (1, 128)),
+           ("V0W", lambda p: p.value_head[0].weight, (128, 128)), ("V0B", lambda p: p.value_head[0].bias, (1, 128)),
+           ("V2W", lambda p: p.value_head[2].weight, (1, 128)), ("V2B", lambda p: p.value_head[2].bias, (1, 1)),
+           ("P0W", lambda p: p.policy_head[0].weight, (128, 128)), ("P0B", lambda p: p.policy_head[0].bias, (1, 128)),
+           ("DW", lambda p: p.dist.linear.weight, (8, 128)), ("DB", lambda p: p.dist.linear.bias, (1, 8)))
+_PF_OFF, PF_FLOATS = _offsets(((k, r * c) for k, _, (r, c) in _PARAMS), align=4)
+_PF = tuple((k, get, _PF_OFF[k]) for k, get, _ in _PARAMS)        # (name, accessor, offset in floats)
+
+# The fold (this file's header) as data, on row-major matrices named as above: a parameter, a plain section (a vector is one
+# row) or "M" = messages.W_val W_out, a scratch matrix; a block of one is (name, (row, column, rows, columns)).
+_MATS = dict([(k, shp) for k, _, shp in _PARAMS] + [(k, shp if len(shp) == 2 else (1,) + shp) for k, shp, _ in SECTIONS],
+             M=(128, 128))
+# copies: (section, row, column) where the block starts <- parameter (block), transposed or not
+_COPIES = (("WE", 0, 0, "ENC_W", True), ("BE", 0, 0, "ENC_B", False), ("WOE", 0, 0, "OENC_W", True), ("BOE", 0, 0, "OENC_B", False),
+           ("W7", 0, 0, ("UW", (0, 0, 128, 128)), True), ("BU", 0, 0, "UB", False),
+           ("W8", 0, 0, "P0W", True), ("W8", 0, 128, "V0W", True), ("B8", 0, 0, "P0B", False), ("B8", 0, 128, "V0B", False),
+           ("W9", 0, 0, "DW", True), ("W9", 128, 8, "V2W", True), ("B9", 0, 0, "DB", False), ("B9", 0, 8, "V2B", False))
+# products C = alpha * A op(B): (C, A, B, B transposed, whose norm_factor alpha is, row chunks = tasks)
+_PRODUCTS = (("AO", "OK", "OQ", True, "oppAttn", 1), ("BO", "OV", "OO", False, None, 1), ("AM", "MQ", "MK", True, "messages", 4),
+             ("M", "MV", "MO", False, None, 4), (("W7", (128, 0, 128, 128)), "M", ("UW", (0, 128, 128, 128)), True, None, 4))
+
+
+def _ref(m):
+    """A matrix or a block of one -> (name, float offset inside the matrix, rows, columns, leading dimension)."""
+    name, blk = (m, None) if isinstance(m, str) else m
+    r0, c0, r, c = blk or (0, 0) + _MATS[name]
+    return name, r0 * _MATS[name][1] + c0, r, c, _MATS[name][1]
+
+
+def _strides(ref, t):
+    """(row, column) stride of op(matrix); one row has row stride 0."""
+    _, _, r, c, ld = ref
+    rs, cs = (ld if r > 1 else 0), 1
+    if t:
+        r, rs, cs = c, cs, rs
+    return (0 if r == 1 else rs), cs
+
+
+def _cp(Cp, c, Ap, a, t):
+    """C = op(A): one copy task."""
+    return dict(C=Cp, ldc=c[4], M=c[2], N=c[3], A=Ap, a=_strides(a, t))
+
+
+def _mm(Cp, c, Ap, a, ta, Bp, b, tb, alpha, split):
+    """C = alpha * op(A) op(B) as `split` row chunks (one task, FA_TASK_SLICES workgroups, each)."""
+    sa, rows = _strides(a, ta), c[2] // split
+    return [dict(C=Cp + 4 * s * rows * c[4], ldc=c[4], M=rows, N=c[3], K=a[2] if ta else a[3], A=Ap + 4 * s * rows * sa[0], a=sa,
+                 B=Bp, b=_strides(b, tb), alpha=alpha) for s in range(split)]
 
 
 class FlatPolicy(object):
@@ -270,17 +298,15 @@ class FlatPolicy(object):
         dev = pol.update[0].weight.device
         z = lambda n: torch.zeros(n, device=dev, dtype=torch.float32)
         self.pflat, self.gflat = z(PF_FLOATS), z(PF_FLOATS + 8)     # + 8: room for loss sums in one all-reduce
-        self.off = {}
         with torch.no_grad():
             for name, get, off in _PF:
                 p = get(pol)
                 n = p.numel()
                 self.pflat[off:off + n].copy_(p.data.reshape(-1))
                 p.data = self.pflat[off:off + n].view(p.shape)
-                self.off[name] = off
         self.plain, self.mscr, self.dmscr = z(PLAIN_FLOATS), z(128 * 128), z(128 * 128)
         self.w, self.wt = z(WEIGHT_FLOATS), z(TRANS_FLOATS)
-        self._fold = [self._tasks(self._fold_stage1()), self._tasks(self._fold_stage2())]
+        self._fold = [self._tasks(s) for s in self._stages()]
         self._unfold = {}       # gradient buffer address -> its two task lists (captured graphs keep the pointers)
         self.attach_grads()
 
@@ -306,37 +332,37 @@ class FlatPolicy(object):
         L, C = self._lib, self._C
         L.check(L.load().fa_run_tasks(tl[0].data_ptr(), tl[1], C.c_void_p(torch.cuda.current_stream().cuda_stream)), "fa_run_tasks")
 
-    @staticmethod
-    def _mm(Cp, ldc, M, N, K, Ap, a, Bp, b, alpha=1.0, split=1):
-        """C (M x N) = alpha * A B as `split` row chunks (one workgroup each)."""
-        out, rows = [], M // split
-        for s in range(split):
-            out.append(dict(C=Cp + 4 * s * rows * ldc, ldc=ldc, M=rows, N=N, K=K, A=Ap + 4 * s * rows * a[0], a=a, B=Bp, b=b, alpha=alpha))
-        return out
+    def _stages(self, gp=None):
+        """The two launches' task lists of the fold (pflat -> plain), or, given the address gp of plain-layout gradients, of
+        its chain rule (gp -> gflat).  Stage 2 holds what reads the scratch that stage 1 writes: M (mscr), dM (dmscr)."""
+        val = (self.pflat.data_ptr(), self.plain.data_ptr(), self.mscr.data_ptr())
+        grd = (self.gflat.data_ptr(), gp, self.dmscr.data_ptr())
 
-    def _fold_stage1(self):
-        th, P, o, po = self.pflat.data_ptr(), self.plain.data_ptr(), self.off, POFF
-        a = lambda name, extra=0: th + 4 * (o[name] + extra)
-        c = lambda name, extra=0: P + 4 * (po[name] + extra)
-        pol = self.pol
-        cp = lambda Cp, ldc, M, N, Ap, ars, acs: dict(C=Cp, ldc=ldc, M=M, N=N, A=Ap, a=(ars, acs))
-        t = [cp(c("WE"), 64, 6, 64, a("ENC_W"), 1, 6), cp(c("BE"), 64, 1, 64, a("ENC_B"), 0, 1),
-             cp(c("WOE"), 64, 6, 64, a("OENC_W"), 1, 6), cp(c("BOE"), 64, 1, 64, a("OENC_B"), 0, 1),
-             cp(c("W7"), 128, 128, 128, a("UW"), 1, 256), cp(c("BU"), 128, 1, 128, a("UB"), 0, 1),
-             cp(c("W8"), 256, 128, 128, a("P0W"), 1, 128), cp(c("W8", 128), 256, 128, 128, a("V0W"), 1, 128),
-             cp(c("B8"), 256, 1, 128, a("P0B"), 0, 1), cp(c("B8", 128), 256, 1, 128, a("V0B"), 0, 1),
-             cp(c("W9"), 32, 128, 8, a("DW"), 1, 128), cp(c("W9", 128 * 32 + 8), 32, 128, 1, a("V2W"), 1, 0),
-             cp(c("B9"), 32, 1, 8, a("DB"), 0, 1), cp(c("B9", 8), 32, 1, 1, a("V2B"), 0, 1)]
-        t += self._mm(c("AO"), 64, 64, 64, 64, a("OK"), (64, 1), a("OQ"), (1, 64), pol.oppAttn.norm_factor)
-        t += self._mm(c("BO"), 64, 64, 64, 64, a("OV"), (64, 1), a("OO"), (64, 1))
-        t += self._mm(c("AM"), 128, 128, 128, 128, a("MQ"), (128, 1), a("MK"), (1, 128), pol.messages.norm_factor, split=4)
-        t += self._mm(self.mscr.data_ptr(), 128, 128, 128, 128, a("MV"), (128, 1), a("MO"), (128, 1), split=4)
-        return t
+        def at(ref, grad=False):        # address of a matrix block, or of its gradient
+            par, sec, scr = grd if grad else val
+            name = ref[0]
+            base = scr if name == "M" else sec + 4 * POFF[name] if name in POFF else par + 4 * _PF_OFF[name]
+            return base + 4 * ref[1]
 
-    def _fold_stage2(self):   # W7[128:] = (W_val W_out) update.weight[:, 128:]^T
-        th, P = self.pflat.data_ptr(), self.plain.data_ptr()
-        return self._mm(P + 4 * (POFF["W7"] + 128 * 128), 128, 128, 128, 128, self.mscr.data_ptr(), (128, 1),
-                        th + 4 * (self.off["UW"] + 128), (1, 256), split=4)
+        back, st = gp is not None, ([], [])
+        for sec, r0, c0, par, t in _COPIES:
+            src = _ref(par)
+            dst = _ref((sec, (r0, c0) + ((src[3], src[2]) if t else (src[2], src[3]))))
+            # a copy's reverse is the (transposed) copy of the gradient
+            st[0].append(_cp(at(src, True), src, at(dst, True), dst, t) if back else _cp(at(dst), dst, at(src), src, t))
+        for C, A, B, tb, norm, split in _PRODUCTS:
+            C, A, B = _ref(C), _ref(A), _ref(B)
+            alpha = getattr(self.pol, norm).norm_factor if norm else 1.0
+            if not back:
+                st["M" in (A[0], B[0])].extend(_mm(at(C), C, at(A), A, False, at(B), B, tb, alpha, split))
+                continue
+            dC, out = at(C, True), st[C[0] == "M"]
+            out.extend(_mm(at(A, True), A, dC, C, False, at(B), B, not tb, alpha, split))     # dA = alpha dC op(B)^T
+            if tb:                                                                            # dB = alpha dC^T A ...
+                out.extend(_mm(at(B, True), B, dC, C, True, at(A), A, False, alpha, split))
+            else:                                                                             # ... or alpha A^T dC
+                out.extend(_mm(at(B, True), B, at(A), A, True, dC, C, False, alpha, split))
+        return st
 
     def fold_pack(self):
         """parameters -> plain kernel-facing matrices -> forward + transposed packs (self.w, self.wt)."""
@@ -349,33 +375,7 @@ class FlatPolicy(object):
 
     def _build_unfold(self, gp):
         """gp: data pointer of the plain-layout gradient buffer (the fa_ppo_grad slab sum)."""
-        th, g, o, po = self.pflat.data_ptr(), self.gflat.data_ptr(), self.off, POFF
-        a = lambda name, extra=0: th + 4 * (o[name] + extra)
-        gr = lambda name, extra=0: g + 4 * (o[name] + extra)
-        d = lambda name, extra=0: gp + 4 * (po[name] + extra)
-        pol = self.pol
-        no, nm = pol.oppAttn.norm_factor, pol.messages.norm_factor
-        cp = lambda Cp, ldc, M, N, Ap, ars, acs: dict(C=Cp, ldc=ldc, M=M, N=N, A=Ap, a=(ars, acs))
-        D = d("W7", 128 * 128)                      # dL/d(W7[128:]) (128 x 128)
-        s1 = [cp(gr("ENC_W"), 6, 64, 6, d("WE"), 1, 64), cp(gr("ENC_B"), 64, 1, 64, d("BE"), 0, 1),
-              cp(gr("OENC_W"), 6, 64, 6, d("WOE"), 1, 64), cp(gr("OENC_B"), 64, 1, 64, d("BOE"), 0, 1),
-              cp(gr("UW"), 256, 128, 128, d("W7"), 1, 128), cp(gr("UB"), 128, 1, 128, d("BU"), 0, 1),
-              cp(gr("P0W"), 128, 128, 128, d("W8"), 1, 256), cp(gr("V0W"), 128, 128, 128, d("W8", 128), 1, 256),
-              cp(gr("P0B"), 128, 1, 128, d("B8"), 0, 1), cp(gr("V0B"), 128, 1, 128, d("B8", 128), 0, 1),
-              cp(gr("DW"), 128, 8, 128, d("W9"), 1, 32), cp(gr("V2W"), 128, 1, 128, d("W9", 128 * 32 + 8), 0, 32),
-              cp(gr("DB"), 8, 1, 8, d("B9"), 0, 1), cp(gr("V2B"), 1, 1, 1, d("B9", 8), 0, 1)]
-        s1 += self._mm(gr("OK"), 64, 64, 64, 64, d("AO"), (64, 1), a("OQ"), (64, 1), no)        # dW_key = norm dA_o W_query
-        s1 += self._mm(gr("OQ"), 64, 64, 64, 64, d("AO"), (1, 64), a("OK"), (64, 1), no)        # dW_query = norm dA_o^T W_key
-        s1 += self._mm(gr("OV"), 64, 64, 64, 64, d("BO"), (64, 1), a("OO"), (1, 64))            # dW_val = dB_o W_out^T
-        s1 += self._mm(gr("OO"), 64, 64, 64, 64, a("OV"), (1, 64), d("BO"), (64, 1))            # dW_out = W_val^T dB_o
-        s1 += self._mm(gr("MQ"), 128, 128, 128, 128, d("AM"), (128, 1), a("MK"), (128, 1), nm, split=4)
-        s1 += self._mm(gr("MK"), 128, 128, 128, 128, d("AM"), (1, 128), a("MQ"), (128, 1), nm, split=4)
-        s1 += self._mm(self.dmscr.data_ptr(), 128, 128, 128, 128, D, (128, 1), a("UW", 128), (256, 1), split=4)   # dM = D Wu2
-        s1 += self._mm(gr("UW", 128), 256, 128, 128, 128, D, (1, 128), self.mscr.data_ptr(), (128, 1), split=4)   # dWu2 = D^T M
-        dm = self.dmscr.data_ptr()
-        s2 = self._mm(gr("MV"), 128, 128, 128, 128, dm, (128, 1), a("MO"), (1, 128), split=4)   # dW_val = dM W_out^T
-        s2 += self._mm(gr("MO"), 128, 128, 128, 128, a("MV"), (1, 128), dm, (128, 1), split=4)  # dW_out = W_val^T dM
-        return [self._tasks(s1), self._tasks(s2)]
+        return [self._tasks(s) for s in self._stages(gp)]
 
     def unfold(self, grads_plain):
         """plain-layout gradients of the kernel-facing matrices (a FA_SLAB buffer) -> gflat (== every parameter's

@@ -146,16 +146,38 @@ def test_buffer_sizes_of_the_binding_match_the_library(fa):
     lib = fa._lib.load()
     assert lib.fa_policy_weight_floats() == mp_.WEIGHT_FLOATS and lib.fa_policy_plain_floats() == mp_.PLAIN_FLOATS
     assert lib.fa_policy_weight_t_floats() == mp_.TRANS_FLOATS and lib.fa_ppo_grad_floats() == mp_.SLAB_FLOATS
-    hdr = open(os.path.join(PKG, "csrc", "fa_policy.h")).read()
-    off = dict((k, int(v)) for k, v in re.findall(r"#define FA_POFF_([A-Z0-9]+)\s+(\d+)", hdr))
-    off3 = dict((k, int(v)) for k, v in re.findall(r"#define FA_POFF3_([A-Z0-9]+)\s+(\d+)", hdr))
-    assert off == mp_.POFF and off3 == mp_.POFF3
-    sizes = dict(AO=64 * 64, BO=64 * 64, AM=128 * 128, W7=256 * 128, W8=128 * 256, W9=256 * 32)
+    hdr = open(os.path.join(PKG, "csrc", "fa_policy.h")).read() + open(os.path.join(PKG, "csrc", "fa_train.h")).read()
+    defs = lambda prefix: dict((k, int(v)) for k, v in re.findall(r"#define %s([A-Z0-9_]+)\s+(\d+)" % prefix, hdr))
+    off, off3, offt = defs("FA_POFF_"), defs("FA_POFF3_"), defs("FA_TOFF_")
+    assert off == mp_.POFF and off3 == mp_.POFF3 and offt == mp_.TOFF
+    assert defs("FA_POLICY_")["PLAIN_FLOATS"] == mp_.PLAIN_FLOATS and defs("FA_POLICY_")["WEIGHT_FLOATS"] == mp_.WEIGHT_FLOATS
+    assert defs("FA_TRANS_")["FLOATS"] == mp_.TRANS_FLOATS
+    sizes = dict((k, shp[0] * shp[1]) for k, shp, dense in mp_.SECTIONS if dense)
+    assert tuple(sizes) == mp_._GEMMS and len(sizes) == 6
     at = mp_.PLAIN_FLOATS
-    for k in ("AO", "BO", "AM", "W7", "W8", "W9"):          # back to back, 1.5 floats per weight, 16-byte aligned
+    for k in mp_._GEMMS:                                     # back to back, 1.5 floats per weight, 16-byte aligned
         assert off3[k] == at and at % 4 == 0, k
         at += sizes[k] * 3 // 2
     assert at == mp_.WEIGHT_FLOATS
+
+
+def test_layout_computed_from_the_section_table_is_the_recorded_layout():
+    """mpnn_pack computes every offset as a running sum over its section / parameter tables: the results are the literals
+    the module held before (recorded here), so nothing a kernel or a saved buffer relies on moved."""
+    from emergent_multiagent_strategies_amd import mpnn_pack as mp_
+    assert mp_.POFF == dict(WE=0, BE=384, WOE=448, BOE=832, AO=896, BO=4992, AM=9088, W7=25472, BU=58240, W8=58368, B8=91136,
+                            W9=91392, B9=99584) and list(mp_.POFF) == [k for k, _, _ in mp_.SECTIONS]
+    assert mp_.POFF3 == dict(AO=99616, BO=105760, AM=111904, W7=136480, W8=185632, W9=234784)
+    assert mp_.TOFF == dict(AOT=0, BOT=4096, AMT=8192, W7T=24576, W8T=57344, W9T=90112)
+    assert mp_.PLAIN_SHAPES == dict(WE=(6, 64), BE=(64,), WOE=(6, 64), BOE=(64,), AO=(64, 64), BO=(64, 64), AM=(128, 128),
+                                    W7=(256, 128), BU=(128,), W8=(128, 256), B8=(256,), W9=(256, 32), B9=(32,))
+    assert list(mp_.PLAIN_SHAPES) == list(mp_.POFF) and mp_._GEMMS == ("AO", "BO", "AM", "W7", "W8", "W9")
+    assert (mp_.PLAIN_FLOATS, mp_.WEIGHT_FLOATS, mp_.TRANS_FLOATS, mp_.SLAB_FLOATS) == (99616, 247072, 98304, 99632)
+    assert [(k, off) for k, _, off in mp_._PF] == [
+        ("ENC_W", 0), ("ENC_B", 384), ("OENC_W", 448), ("OENC_B", 832), ("OQ", 896), ("OK", 4992), ("OV", 9088), ("OO", 13184),
+        ("MQ", 17280), ("MK", 33664), ("MV", 50048), ("MO", 66432), ("UW", 82816), ("UB", 115584), ("V0W", 115712),
+        ("V0B", 132096), ("V2W", 132224), ("V2B", 132352), ("P0W", 132356), ("P0B", 148740), ("DW", 148868), ("DB", 149892)]
+    assert mp_.PF_FLOATS == 149900
 
 
 def test_one_call_tail_refuses_null_arguments(fa):
